@@ -1,8 +1,14 @@
 """Benchmark: GbmCVNNPricer training steps on MI355X (BASELINE.json metric / config C2).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1] [--store all|terminal]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...);
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  `--full`
+adds every figure that takes runs of its own: the roofline object, the network part alone, the measured HBM
+ceilings, the isolated all-reduce and the CPU baseline.
 
 A "step" is one full training step (reference gbm_trainer.py:1532-1597): Sobol draw of B
 contracts, GBM simulation of P paths x T steps per contract (full [B][T][P] path matrix
@@ -11,7 +17,7 @@ M-batch mean + N-point DFT -> targets, CVNN forward/backward, Adam, grad norm.  
 every rank processes B contracts per step (contract-sharded data parallel, one RCCL all-reduce).
 
 Rank 0 prints ONE JSON line.  `value` = contracts x paths per second over the whole job.
-The roofline object is for the dominant kernel (the MC part of the step: resident_kernel at C2,
+With --full the roofline object is for the dominant kernel (the MC part of the step: resident_kernel at C2,
 its sliced form at C3, basket_resident_kernel at C5): algorithmic bytes per launch over the
 launch's duration, timed with HIP events on its own stream right after the timed region (`kernel_ms`;
 `kernel_ms_live` / `kernel_ms_steady`: the launches inside the timed region).  `cpu_baseline` is the
@@ -112,9 +118,17 @@ def parse(argv: list[str] | None = None) -> argparse.Namespace:
                     help="CUs reserved for a wide (layered GEMM) network (pricer.network_cus_wide)")
     ap.add_argument("--net-cu-pattern", default="low", choices=["spread", "low"])
     ap.add_argument("--graphs", default="on", choices=["on", "off"], help="replay the step as hipGraphs")
-    ap.add_argument("--kernel-iters", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget for the CPU-baseline sample")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the dominant kernel alone "
+                         "(roofline), the network part alone, the HBM ceilings, the isolated all-reduce and the CPU "
+                         "baseline")
+    ap.add_argument("--kernel-iters", type=int, default=10, help="with --full: launches of the kernel-alone timings")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="with --full: budget for the CPU-baseline sample")
     return ap.parse_args(argv)
 
 
@@ -339,6 +353,48 @@ def make_pricer(args: argparse.Namespace, dev):
     return pricer, model
 
 
+DUMP_BYTES = 60 * 10**6  # --dump-outputs: the arrays hold at most this much in all (the files stay under 64 MB)
+
+
+def dump_outputs(out_dir: str, session, model, final, rank: int = 0, world: int = 1) -> dict[str, list[int]]:
+    """What the last timed step computed, as ``out_dir/<name>.npy`` (float32 / float64): the step slot the
+    step's MC part wrote (``contracts``: the Sobol draw; ``network_input``: the CVNN's real input;
+    ``targets``: the complex DFT targets as (B, N, [re, im])) and what the training run hands its caller
+    (``parameters``: every CVNN parameter after the last step, flattened in ``model.parameters()`` order;
+    ``loss_grad_norm``: the last step's loss and gradient norm).  Call after ``session.close()``.  An array
+    that does not fit what is left of DUMP_BYTES is cut to a fixed, seeded sample of its rows (seed 0, rows
+    in ascending order), so two builds run with the same arguments write the same rows.  Data-parallel runs
+    write one set per rank (``<name>_rank<r>.npy``, each within DUMP_BYTES / world).  Returns {name: shape}."""
+    import numpy as np
+    import torch
+
+    prog = session.program
+    slot = prog.slots[(session.steps - 1) % len(prog.slots)]
+    arrays = {
+        "loss_grad_norm": torch.tensor([final.loss, final.grad_norm], dtype=torch.float64),
+        "parameters": torch.cat([p.detach().reshape(-1) for p in model.parameters()]),
+        "network_input": slot.real_in,
+        "targets": torch.view_as_real(slot.targets),
+    }
+    if prog.direct:  # (a hand-off copy fills the slot's network input and targets only)
+        arrays["contracts"] = slot.contracts
+    os.makedirs(out_dir, exist_ok=True)
+    left, shapes = DUMP_BYTES // world, {}
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size()):
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float32)
+        row_bytes = max(1, t[0].numel() * t.element_size()) if t.dim() > 1 else t.element_size()
+        rows = min(t.shape[0], left // row_bytes)
+        if rows < t.shape[0]:
+            keep = np.sort(np.random.default_rng(0).choice(t.shape[0], rows, replace=False))
+            t = t[torch.from_numpy(keep).to(t.device)]
+        a = np.ascontiguousarray(t.cpu().numpy())
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def launcher_command(argv: list[str], gpus: int, port: int, script: str | None = None) -> list[str]:
     """The torch.distributed.run command that starts `gpus` ranks of this script with the same arguments
     (the driver's own form: one node, 127.0.0.1 rendezvous)."""
@@ -365,6 +421,18 @@ def maybe_launch_ranks(args: argparse.Namespace, argv: list[str], script: str | 
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC (RCCL between processes)
     return subprocess.call(launcher_command(argv, args.gpus, free_port(), script), env=env)
+
+
+def finish(ctx) -> None:
+    """End of a rank's run: leave the process group (data-parallel runs)."""
+    if ctx:
+        import torch.distributed as dist
+
+        from spectralmc_amd import dp
+
+        dist.barrier()
+        dp.shutdown()
+        dist.destroy_process_group()
 
 
 def main() -> None:
@@ -406,16 +474,18 @@ def main() -> None:
     if ctx:
         dist.barrier()
     torch.cuda.synchronize()
-    # HIP events around each MC-part launch on its stream (timed region), created and recorded once beforehand
-    pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps + 2)]
-    for e0, e1 in pool:
-        e0.record()
-        e1.record()
-    torch.cuda.synchronize()
-    session.mc_event_pool = pool[::-1]
-    session.mc_events = []
-    if ctx:
-        session.program.ar_events = []  # ... and around each step's all-reduce on the network stream
+    if args.full:
+        # HIP events around each MC-part launch on its stream (timed region), created and recorded once beforehand
+        pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                for _ in range(args.steps + 2)]
+        for e0, e1 in pool:
+            e0.record()
+            e1.record()
+        torch.cuda.synchronize()
+        session.mc_event_pool = pool[::-1]
+        session.mc_events = []
+        if ctx:
+            session.program.ar_events = []  # ... and around each step's all-reduce on the network stream
     t0 = time.perf_counter()
     for _ in range(args.steps):
         expect_success(session.step())
@@ -430,6 +500,44 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final = session.close()
+
+    total_units = world * B * P * args.steps
+    value = total_units / elapsed
+    fused = session.program.fused
+    line = {
+        "metric": "training-steps/sec (contracts*paths/s) + HBM GB/s, GBM 4096x65536"
+                  + (f" [{args.config}: basket of {n_assets} correlated assets]" if n_assets else ""),
+        "value": value,
+        "unit": "contracts*paths/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "host_enqueue_ms_per_step": t_enq / args.steps * 1e3,
+        "steps_per_sec": args.steps / elapsed,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64" if f64 else "f32",
+        "network_dtype": ("f64" if f64 else
+                          {"mfma_bf16": "bf16 operands, f32 accumulate / master weights"}.get(fused.kernels, "f32")
+                          if fused is not None else "f32 (torch-ROCm modules)"),
+        "data": ("synthetic: Sobol basket contracts (seed 7, basket.default_basket_bounds), random-init CVNN (seed 123)"
+                 if n_assets else
+                 "synthetic: Sobol contracts (seed 7, make_domain_bounds defaults), random-init CVNN (seed 123)"),
+        "config": {"workload": desc, "contracts_per_gpu": B, "global_contracts": world * B, "paths": P,
+                   "timesteps": T, "network_size": N, "batches_per_mc_run": M, "assets": n_assets or 1,
+                   "path_store": args.store, "math": args.math, "parallelism": f"dp{world}"},
+        "full": args.full,
+        "final_loss": final.loss,
+    }
+    if args.dump_outputs:
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs, session, model, final, rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        finish(ctx)
+        return
 
     # ---- data parallel: the step's one all-reduce (flat [grads..., loss] buffer) -----------------
     data_parallel = None
@@ -630,32 +738,7 @@ def main() -> None:
         except (OSError, ValueError, KeyError):
             traffic, traffic_src = None, None
 
-    total_units = world * B * P * args.steps
-    value = total_units / elapsed
-    line = {
-        "metric": "training-steps/sec (contracts*paths/s) + HBM GB/s, GBM 4096x65536"
-                  + (f" [{args.config}: basket of {n_assets} correlated assets]" if n_assets else ""),
-        "value": value,
-        "unit": "contracts*paths/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "host_enqueue_ms_per_step": t_enq / args.steps * 1e3,
-        "steps_per_sec": args.steps / elapsed,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64" if f64 else "f32",
-        "network_dtype": ("f64" if f64 else
-                          {"mfma_bf16": "bf16 operands, f32 accumulate / master weights"}.get(network["compute"], "f32")
-                          if network else "f32 (torch-ROCm modules)"),
-        "data": ("synthetic: Sobol basket contracts (seed 7, basket.default_basket_bounds), random-init CVNN (seed 123)"
-                 if n_assets else
-                 "synthetic: Sobol contracts (seed 7, make_domain_bounds defaults), random-init CVNN (seed 123)"),
-        "config": {"workload": desc, "contracts_per_gpu": B, "global_contracts": world * B, "paths": P,
-                   "timesteps": T, "network_size": N, "batches_per_mc_run": M, "assets": n_assets or 1,
-                   "path_store": args.store, "math": args.math, "parallelism": f"dp{world}"},
+    line.update({
         "roofline": {"bound": "hbm", "kernel": eng.kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "traffic_source": traffic_src,
@@ -702,8 +785,7 @@ def main() -> None:
                      "frac_of_measured_write": (achieved / stream_gbs["write"]) if "write" in stream_gbs else None},
         "network": network,
         "data_parallel": data_parallel,
-        "final_loss": final.loss,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(B, T, N, M, widths, args.cpu_seconds, n_assets, "float64" if f64 else "float32",
                           normalize=args.config not in RAW_NORMALIZATION)
@@ -711,10 +793,7 @@ def main() -> None:
         line["speedup_vs_cpu"] = value / cb["value"]
     if rank == 0:
         print(json.dumps(line), flush=True)
-    if ctx:
-        dist.barrier()
-        dp.shutdown()
-        dist.destroy_process_group()
+    finish(ctx)
 
 
 if __name__ == "__main__":

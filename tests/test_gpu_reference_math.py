@@ -1,5 +1,5 @@
 """SMC_MATH_REF on the GPU (rows_ref_kernel + cf_kernel): the reference kernel's own f32 typing
-(/root/reference/src/spectralmc/gbm.py:224-257 under Numba: f64 state and step of the f32 normals, f32
+(the reference's src/spectralmc/gbm.py:224-257 under Numba: f64 state and step of the f32 normals, f32
 stores).  Bit-exact against the oracle's kernel mode with MATH_REF (stored paths, terminal sums, targets;
 tests/test_oracle.py pins that mode to the reference arithmetic's stored paths), smc_train_step in this
 mode equal to draw + smc_train_targets, and the trainer's math_mode="reference" one step against the

@@ -29,29 +29,29 @@ for step in "$@"; do
     trainer) run trainer 900 python -m pytest tests/test_gpu_trainer.py -q -rf ;;
     gputests) run gputests 1200 python -m pytest tests -m gpu -q -rf ;;
     smoke)   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)   run bench 600 python bench.py ;;
-    bench_quick) run bench_quick 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --math portable ;;
-    bench_hw) run bench_hw 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --math hw ;;
-    bench_hw_terminal) run bench_hw_terminal 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --store terminal --math hw ;;
-    bench_terminal) run bench_terminal 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --store terminal --math portable ;;
-    bench_c1) run bench_c1 600 python bench.py --config c1 --steps 50 --warmup 5 --no-cpu-baseline ;;
+    bench)   run bench 600 python bench.py --full ;;
+    bench_quick) run bench_quick 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --math portable ;;
+    bench_hw) run bench_hw 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --math hw ;;
+    bench_hw_terminal) run bench_hw_terminal 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --store terminal --math hw ;;
+    bench_terminal) run bench_terminal 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --store terminal --math portable ;;
+    bench_c1) run bench_c1 600 python bench.py --config c1 --steps 50 --warmup 5 --full --no-cpu-baseline ;;
     basket)  run basket 600 python -u -m pytest tests/test_gpu_basket.py -x -v --timeout 120 --timeout-method thread -rf ;;
     dp)      run dp 600 python -u -m pytest tests/test_gpu_dp.py -x -v --timeout 300 --timeout-method thread -rf ;;
-    bench_c5) run bench_c5 600 python bench.py --config c5 --steps 10 --warmup 3 --kernel-iters 2 ;;
-    prof_c5) cd /tmp && run prof_c5 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c5" -o run --output-format csv -- python "$ROOT/bench.py" --config c5 --steps 5 --warmup 2 --kernel-iters 1 --no-cpu-baseline; cd "$ROOT" ;;
-    bench_h256) run bench_h256 600 python bench.py --config c2h256 --steps 20 --warmup 3 --no-cpu-baseline ;;
-    bench_seq) run bench_seq 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --overlap off ;;
-    prof_seq) cd /tmp && run prof_seq 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_seq" -o run --output-format csv -- python "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --overlap off; cd "$ROOT" ;;
-    bench_nograph) run bench_nograph 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --graphs off ;;
-    bench_seq_nograph) run bench_seq_nograph 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --graphs off --overlap off ;;
-    bench_q) run bench_q 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline ;;
-    bench_valu) run bench_valu 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --network valu ;;
-    bench_c3_f32) run bench_c3_f32 900 python bench.py --config c3 --steps 3 --warmup 2 --kernel-iters 1 --no-cpu-baseline --network mfma ;;
+    bench_c5) run bench_c5 600 python bench.py --config c5 --steps 10 --warmup 3 --full --kernel-iters 2 ;;
+    prof_c5) cd /tmp && run prof_c5 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c5" -o run --output-format csv -- python "$ROOT/bench.py" --config c5 --steps 5 --warmup 2 --kernel-iters 1 --full --no-cpu-baseline; cd "$ROOT" ;;
+    bench_h256) run bench_h256 600 python bench.py --config c2h256 --steps 20 --warmup 3 --full --no-cpu-baseline ;;
+    bench_seq) run bench_seq 600 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --overlap off ;;
+    prof_seq) cd /tmp && run prof_seq 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_seq" -o run --output-format csv -- python "$ROOT/bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline --overlap off; cd "$ROOT" ;;
+    bench_nograph) run bench_nograph 600 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --graphs off ;;
+    bench_seq_nograph) run bench_seq_nograph 600 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --graphs off --overlap off ;;
+    bench_q) run bench_q 600 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline ;;
+    bench_valu) run bench_valu 600 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --network valu ;;
+    bench_c3_f32) run bench_c3_f32 900 python bench.py --config c3 --steps 3 --warmup 2 --kernel-iters 1 --full --no-cpu-baseline --network mfma ;;
     gputests_v) run gputests_v 1100 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread -p no:cacheprovider -rf ;;
-    bench_c3) run bench_c3 900 python bench.py --config c3 --steps 3 --warmup 2 --kernel-iters 1 --no-cpu-baseline ;;
-    prof)    cd /tmp && run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline; cd "$ROOT" ;;
-    prof_default) cd /tmp && run prof_default 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof_default" -o run --output-format csv -- python "$ROOT/bench.py"; cd "$ROOT" ;;
-    prof_hw) cd /tmp && run prof_hw 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_hw" -o run --output-format csv -- python "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --math hw; cd "$ROOT" ;;
+    bench_c3) run bench_c3 900 python bench.py --config c3 --steps 3 --warmup 2 --kernel-iters 1 --full --no-cpu-baseline ;;
+    prof)    cd /tmp && run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python "$ROOT/bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline; cd "$ROOT" ;;
+    prof_default) cd /tmp && run prof_default 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof_default" -o run --output-format csv -- python "$ROOT/bench.py" --full; cd "$ROOT" ;;
+    prof_hw) cd /tmp && run prof_hw 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_hw" -o run --output-format csv -- python "$ROOT/bench.py" --steps 10 --warmup 3 --full --no-cpu-baseline --math hw; cd "$ROOT" ;;
     pmc_c5_sq) cd /tmp && run pmc_c5_sq 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE -d "$OUT/pmc_c5_sq" -o run --output-format csv -- python "$ROOT/tools/kprof_basket.py"; cd "$ROOT" ;;
     pmc_c5_write) cd /tmp && run pmc_c5_write 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_c5_write" -o run --output-format csv -- python "$ROOT/tools/kprof_basket.py"; cd "$ROOT" ;;
     pmc_c5_fetch) cd /tmp && run pmc_c5_fetch 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_c5_fetch" -o run --output-format csv -- python "$ROOT/tools/kprof_basket.py"; cd "$ROOT" ;;
@@ -72,13 +72,13 @@ for step in "$@"; do
       cd /tmp && run "pmc_${cfg}_${ctr}" 300 rocprofv3 --kernel-trace --pmc "$ctr" -d "$OUT/pmc_${cfg}_${ctr}" -o run --output-format csv -- python "$ROOT/tools/kprof_step.py" --config "$cfg" --iters "${its:-3}"; cd "$ROOT" ;;
     profbench:*)  # profbench:<config>[:steps] -> rocprofv3 kernel stats of bench.py (no CPU leg)
       IFS=: read -r _ cfg st <<< "$step"
-      cd /tmp && run "prof_${cfg}" 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof_${cfg}" -o run --output-format csv -- python "$ROOT/bench.py" --config "$cfg" --steps "${st:-5}" --warmup 2 --kernel-iters 2 --no-cpu-baseline; cd "$ROOT" ;;
+      cd /tmp && run "prof_${cfg}" 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof_${cfg}" -o run --output-format csv -- python "$ROOT/bench.py" --config "$cfg" --steps "${st:-5}" --warmup 2 --kernel-iters 2 --full --no-cpu-baseline; cd "$ROOT" ;;
     profstep:*)  # profstep:<config>[:iters] -> rocprofv3 kernel stats of the MC launch alone (tools/kprof_step.py)
       IFS=: read -r _ cfg its <<< "$step"
       cd /tmp && run "profstep_${cfg}" 300 rocprofv3 --kernel-trace --stats -d "$OUT/profstep_${cfg}" -o run --output-format csv -- python "$ROOT/tools/kprof_step.py" --config "$cfg" --iters "${its:-10}"; cd "$ROOT" ;;
     benchcfg:*)  # benchcfg:<config>[:steps] -> bench.py line with the CPU baseline
       IFS=: read -r _ cfg st <<< "$step"
-      run "bench_${cfg}" 900 python bench.py --config "$cfg" --steps "${st:-10}" --warmup 3 --kernel-iters 2 ;;
+      run "bench_${cfg}" 900 python bench.py --config "$cfg" --steps "${st:-10}" --warmup 3 --full --kernel-iters 2 ;;
     kstep:*)  # kstep:<config>[:extra args with , for spaces]
       IFS=: read -r _ cfg extra <<< "$step"
       run "kstep_${cfg}" 300 python tools/kprof_step.py --config "$cfg" ${extra//,/ } ;;
@@ -87,7 +87,7 @@ for step in "$@"; do
       cd /tmp && run "pmcf64_$tag" 300 rocprofv3 --kernel-trace --pmc ${ctrs//,/ } -d "$OUT/pmcf64_$tag" -o run --output-format csv -- python "$ROOT/tools/kprof_step.py" --config c2 --dtype f64 --iters 3; cd "$ROOT" ;;
     benchx:*)  # benchx:<tag>:<bench args with , for spaces> (no CPU leg)
       IFS=: read -r _ tag args <<< "$step"
-      run "benchx_$tag" 600 python bench.py --no-cpu-baseline ${args//,/ } ;;
+      run "benchx_$tag" 600 python bench.py --full --no-cpu-baseline ${args//,/ } ;;
     tests:*)  # tests:<tag>:<limit s>:<pytest targets / args with , for spaces>
       IFS=: read -r _ tag lim targets <<< "$step"
       run "tests_$tag" "$lim" python -u -m pytest ${targets//,/ } -m gpu -v -x --timeout 300 --timeout-method thread -p no:cacheprovider -rf ;;

@@ -17,8 +17,8 @@ step() {  # name limit cmd...
 for cfg in "$@"; do
   steps=20
   [ "$cfg" = c3 ] || [ "$cfg" = c5 ] && steps=5
-  step bench_$cfg 420 python bench.py --config $cfg --steps $steps
-  step prof_$cfg 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -- python3 bench.py --config $cfg --no-cpu-baseline --steps $steps
+  step bench_$cfg 420 python bench.py --full --config $cfg --steps $steps
+  step prof_$cfg 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -- python3 bench.py --config $cfg --full --no-cpu-baseline --steps $steps
   case "$cfg" in
     c5) drv="tools/kprof_basket.py" ;;
     c2h256) drv="tools/kprof_step.py --config c2 --iters 5" ;;

@@ -18,9 +18,9 @@ step() {  # name limit cmd...
 for cfg in "$@"; do
   steps=20; warm=3
   case "$cfg" in c3|c5) steps=5; warm=2 ;; c2f64) steps=10 ;; esac
-  if [ "$cfg" = c2 ]; then step bench_c2 420 python bench.py; else step bench_$cfg 420 python bench.py --config $cfg --steps $steps --warmup $warm; fi
+  if [ "$cfg" = c2 ]; then step bench_c2 420 python bench.py --full; else step bench_$cfg 420 python bench.py --config $cfg --steps $steps --warmup $warm --full; fi
   cd /tmp
-  step prof_$cfg 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -o run -- python3 $ROOT/bench.py --config $cfg --no-cpu-baseline --steps $steps --warmup $warm
+  step prof_$cfg 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -o run -- python3 $ROOT/bench.py --config $cfg --full --no-cpu-baseline --steps $steps --warmup $warm
   case "$cfg" in
     c2|c2h256) drv="$ROOT/tools/kprof_step.py --config c2 --dynamic --iters 10" ;;
     c3) drv="$ROOT/tools/kprof_step.py --config c3 --iters 4" ;;

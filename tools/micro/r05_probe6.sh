@@ -13,6 +13,6 @@ for rep in 1 2; do
       SMC_LIB_PATH=$L timeout -k 10 120 python tools/kprof_net.py --arch h256 $opt 2>/dev/null | grep -v amdgpu.ids >> $O/net_h256.txt || exit $?
     done
     echo -n "$lib c2h256: " >> $O/bench_h256.txt
-    SMC_LIB_PATH=$L timeout -k 10 200 python bench.py --config c2h256 --steps 20 --warmup 3 --kernel-iters 2 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'net', round(d['network']['ms'],4))" >> $O/bench_h256.txt || exit $?
+    SMC_LIB_PATH=$L timeout -k 10 200 python bench.py --config c2h256 --steps 20 --warmup 3 --kernel-iters 2 --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'net', round(d['network']['ms'],4))" >> $O/bench_h256.txt || exit $?
   done
 done

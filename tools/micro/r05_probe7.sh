@@ -15,9 +15,9 @@ for rep in 1 2; do
     done
     for cfg in c2h256 c2 e2e; do
       echo -n "$lib $cfg: " >> $O/bench.txt
-      SMC_LIB_PATH=$L timeout -k 10 200 python bench.py --config $cfg --steps 20 --warmup 3 --kernel-iters 2 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'net', round(d['network']['ms'],4))" >> $O/bench.txt || exit $?
+      SMC_LIB_PATH=$L timeout -k 10 200 python bench.py --config $cfg --steps 20 --warmup 3 --kernel-iters 2 --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'net', round(d['network']['ms'],4))" >> $O/bench.txt || exit $?
     done
     echo -n "$lib lockstep: " >> $O/bench.txt
-    [ $lib = default ] && { SMC_LIB_PATH=$L timeout -k 10 200 python bench.py --config lockstep --steps 40 --warmup 3 --kernel-iters 2 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'net', round(d['network']['ms'],4))" >> $O/bench.txt || exit $?; } || echo "(r4 library: RAW query flag of ABI 11)" >> $O/bench.txt
+    [ $lib = default ] && { SMC_LIB_PATH=$L timeout -k 10 200 python bench.py --config lockstep --steps 40 --warmup 3 --kernel-iters 2 --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'net', round(d['network']['ms'],4))" >> $O/bench.txt || exit $?; } || echo "(r4 library: RAW query flag of ABI 11)" >> $O/bench.txt
   done
 done

@@ -6,7 +6,7 @@ O=gpurun_out/r05p8; mkdir -p $O
 run() {  # tag args...
   local tag=$1; shift
   echo -n "$tag: " >> $O/netcus.txt
-  timeout -k 10 200 python bench.py --steps 40 --warmup 3 --kernel-iters 2 --no-cpu-baseline "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4))" >> $O/netcus.txt || exit $?
+  timeout -k 10 200 python bench.py --steps 40 --warmup 3 --kernel-iters 2 --full --no-cpu-baseline "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4))" >> $O/netcus.txt || exit $?
 }
 for rep in 1 2; do
   for c in 32 64 96; do run "lockstep net_cus=$c" --config lockstep --net-cus $c || exit $?; done

@@ -9,7 +9,7 @@ for rep in 1 2; do
   for gb in default 97; do
     echo -n "budget=$gb: " >> $o
     if [ $gb = default ]; then env_=""; else env_="SMC_PATH_BUFFER_GB=$gb"; fi
-    env $env_ timeout -k 10 300 python bench.py --config c5 --steps 5 --warmup 2 --kernel-iters 1 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(f\"{d['ms_per_step']:.3f} ms/step, {r['contracts_per_launch']} per launch, kernel {r['kernel_ms']:.3f}\")" >> $o || exit 1
+    env $env_ timeout -k 10 300 python bench.py --config c5 --steps 5 --warmup 2 --kernel-iters 1 --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(f\"{d['ms_per_step']:.3f} ms/step, {r['contracts_per_launch']} per launch, kernel {r['kernel_ms']:.3f}\")" >> $o || exit 1
   done
 done
 cat $o

@@ -35,9 +35,9 @@ for cfg in "$@"; do
   fi
   steps=20; warm=3; args="--config $cfg"
   case "$cfg" in c3|c5) steps=5; warm=2 ;; c2f64) steps=10 ;; c2ref) steps=10; args="--config c2 --math reference" ;; c2refhw) steps=10; args="--config c2 --math reference_hw" ;; esac
-  if [ "$cfg" = c2 ]; then step bench_c2 420 python bench.py; else step bench_$cfg 420 python bench.py $args --steps $steps --warmup $warm --no-cpu-baseline; fi
+  if [ "$cfg" = c2 ]; then step bench_c2 420 python bench.py --full; else step bench_$cfg 420 python bench.py $args --steps $steps --warmup $warm --full --no-cpu-baseline; fi
   cd /tmp
-  step prof_$cfg 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -o run -- python3 $ROOT/bench.py $args --no-cpu-baseline --steps $steps --warmup $warm
+  step prof_$cfg 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -o run -- python3 $ROOT/bench.py $args --full --no-cpu-baseline --steps $steps --warmup $warm
   case "$cfg" in
     c2|c2h256) drv="$ROOT/tools/kprof_step.py --config c2 --dynamic --iters 10" ;;
     c3) drv="$ROOT/tools/kprof_step.py --config c3 --iters 4" ;;
