@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 15  /* 14: smc_time_launches; 15: SMC_MATH_REF | SMC_MATH_HW */
+#define SMC_ABI_VERSION 16  /* 14: smc_time_launches; 15: SMC_MATH_REF | SMC_MATH_HW; 16: smc_gbm_price */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -370,6 +370,31 @@ int32_t smc_cvnn_mfma_forward_backward(const smc_cvnn_layer* layers, int32_t n_l
  * wide layers keep their own pack launch (the layered GEMM path). */
 int32_t smc_cvnn_mfma_pack_plan(const smc_cvnn_layer* layers, int32_t n_layers, int32_t mode, int64_t batch,
                                 void* workspace, smc_cvnn_pack* out);
+
+/* ---- batched Monte-Carlo pricing (ABI 16) -----------------------------------
+ * BlackScholes.price + get_host_price (src/spectralmc/gbm.py:442-497) for B contracts in ONE launch:
+ * one workgroup per contract simulates the P paths in the simulate call's order (same streams: contract b
+ * uses ordinal (*ordinal_dev or 0) + ordinal0 + b) and writes no path row: the terminal values stay on
+ * chip and leave as SMC_PRICE_COLS doubles per contract, prices_dev [B][8]:
+ *   0 put price, 1 call price, 2 underlying (means over the P paths of df max(K - xs, 0),
+ *   df max(xs - K, 0) and xs, each evaluated in the sim dtype as the CF targets' payoff is and added in f64;
+ *   xs = x F / mean(x) under SMC_NORM_NORMALIZE, x under SMC_NORM_RAW),
+ *   3 put / 4 call standard error of that mean (0 at P = 1), 5 put / 6 call intrinsic value
+ *   df max(K - F, 0) / df max(F - K, 0), 7 the f64 sum of the raw terminal values.
+ * Every sum has one fixed order: the block is bit-identical run to run, under any split of the batch and
+ * whichever way the kernel keeps the terminal values (NORMALIZE needs them twice: parked in LDS for
+ * contracts of up to 144 KiB of terminal values, else simulated a second time; SMC_PRICE_REPLAY forces the
+ * latter).  scheme takes SMC_MATH_HW (f32 only); SMC_MATH_REF is rejected.  B below the CU count leaves
+ * CUs idle (a contract is not split over workgroups). */
+#define SMC_PRICE_COLS   8
+#define SMC_PRICE_REPLAY 0x800   /* flag, OR into the price call's scheme: never park in LDS */
+int32_t smc_gbm_price(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
+                      uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
+                      int32_t normalization, int32_t dtype, double* prices_dev /*[B][8]*/, void* stream);
+/* Name of the kernel that call launches for this shape: "price_kernel(raw)", "price_kernel(lds)",
+ * "price_kernel(replay)", or "unsupported".  Static string, no device call. */
+const char* smc_gbm_price_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                 int32_t dtype);
 
 #ifdef __cplusplus
 }

@@ -40,7 +40,9 @@ TRAIN_DYNAMIC = 0x200
 MATH_REF = 0x400  # the reference kernel's typing: f64 state and step, f32 normals and stores
 STORE_ALL = 2
 SOBOL_BITS = 30
-ABI_VERSION = 15
+PRICE_REPLAY = 0x800  # smc_gbm_price scheme flag: never park the terminal values in LDS
+PRICE_COLS = 8  # doubles per contract smc_gbm_price writes
+ABI_VERSION = 16
 
 _c_i32, _c_i64, _c_u64, _c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
 
@@ -74,6 +76,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_train_targets_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i64, _c_i32]),
     "smc_path_pitch": (_c_i64, [_c_i64, _c_i32]),
     "smc_normals": (_c_i32, [_c_u64, _c_i64, _c_i32, _c_i64, _c_i32, _c_vp, _c_vp]),
+    "smc_gbm_price": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32,
+                               _c_vp, _c_vp]),
+    "smc_gbm_price_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
     "smc_cvnn_plan": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_c_i64)]),
     "smc_cvnn_forward_backward": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64,
                                            _c_vp, _c_i64, _c_vp]),

@@ -329,7 +329,8 @@ __device__ __forceinline__ void lane_paths(const EngineArgs& a, const Stepper<Re
 // lane_rows_s: the same on a stream the caller positioned at the group's first draw (wave_kernel walks
 // a whole stream span, smc_rng.h).
 // stage (LDS, optional): the rows go there instead of to HBM, row r at stage + r * stage_stride + 4 lane_id
-template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL>
+// STORE = false (with !STORE_ALL, price_kernel): no row is written anywhere, the terminal values only go to x_out
+template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL, bool STORE = true>
 __device__ __forceinline__ void lane_rows_s(PathStream& s, const Stepper<Real, LOG_EULER, HW>& step, Real x0,
                                             int64_t chunk, Real* contract_base, int T, int64_t pitch, double& acc,
                                             Real (&x_out)[kPathsPerLane], int lane_id, Real* stage = nullptr,
@@ -345,7 +346,7 @@ __device__ __forceinline__ void lane_rows(const EngineArgs& a, const Stepper<Rea
   lane_rows_s<Real, LOG_EULER, HW, STORE_ALL>(s, step, x0, chunk, contract_base, T, pitch, acc, x_out, lane_id);
 }
 
-template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL>
+template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL, bool STORE>
 __device__ __forceinline__ void lane_rows_s(PathStream& s, const Stepper<Real, LOG_EULER, HW>& step, Real x0,
                                             int64_t chunk, Real* contract_base, int T, int64_t pitch, double& acc,
                                             Real (&x_out)[kPathsPerLane], int lane_id, Real* stage,
@@ -410,7 +411,7 @@ __device__ __forceinline__ void lane_rows_s(PathStream& s, const Stepper<Real, L
     advance(zl);
     if constexpr (STORE_ALL) store();
   }
-  if constexpr (!STORE_ALL) store();
+  if constexpr (!STORE_ALL && STORE) store();
   Real part = 0;
 #pragma unroll
   for (int j = 0; j < kPathsPerLane; ++j) {
@@ -1680,6 +1681,161 @@ __global__ __launch_bounds__(256) void normalize_kernel(const double* __restrict
   }
 }
 
+// ---- batched pricing: price_kernel (smc_gbm_price) ---------------------------------------------
+// One workgroup per contract in simulate_contract's shape and order (512 lanes, 4 consecutive paths
+// per lane and 2048-path chunk, the stream PathStream(seed, ordinal, p0 / 4, T)), through the rolled
+// path loop lane_rows_s with no row store: the terminal values stay on chip and leave as
+// SMC_PRICE_COLS doubles per contract.  Every sum is f64 in one fixed order (per lane over its chunks
+// and, within a chunk, its paths in ascending order; wave butterfly xor 32..1; waves 0..7), so the
+// block is bit-identical run to run, under any split of the batch and in every mode.  The terminal
+// sum adds the lane's 4 values in Real first (lane_paths' order): for f32 it is oracle kernel mode's
+// (wg = 512) bit for bit.  Lanes of the ragged last chunk wholly past P neither draw nor contribute
+// (each lane group has a stream of its own).
+//   kPriceRaw     RAW normalisation: one pass, the payoffs accumulated as the paths finish;
+//   kPriceLds     NORMALIZE: each lane parks its terminal values in dynamic LDS (P Reals) and takes
+//                 the payoffs from there once the sum is known;
+//   kPriceReplay  NORMALIZE, the contract too large to park (or SMC_PRICE_REPLAY): pass 1 gives the
+//                 sum only, pass 2 re-creates the same streams: kPriceLds' values and order.
+enum PriceMode : int { kPriceRaw = 0, kPriceLds = 1, kPriceReplay = 2 };
+constexpr int kPriceSums = 5;  // put, call, underlying, put^2, call^2
+constexpr size_t kPriceScratch = kWaves * kPriceSums * sizeof(double);
+// Largest dynamic LDS (parked terminal row + reduction scratch) of the lds mode; larger contracts replay.
+// Parking beat replaying 1.8-2.1x at every size timed (P = 4096 .. 32,768 f32, also where 128 KiB of parked
+// row leave one workgroup per CU: DESIGN.md 3.2f), so the bound is what a workgroup can hold: 144 KiB, and
+// for f64 what the static table image leaves of the CU's 160 KiB (price_mode).  The choice changes no
+// output bit.  (A macro so an A/B build can move it.)
+#ifndef SMC_PRICE_PARK_BYTES
+#define SMC_PRICE_PARK_BYTES (144 * 1024)
+#endif
+constexpr size_t kPriceParkBytes = SMC_PRICE_PARK_BYTES;
+
+// Sums v[0..K) over the workgroup in the fixed order; every thread gets the totals.  scratch: [kWaves][K].
+template <int K>
+__device__ __forceinline__ void price_reduce(double (&v)[K], double* scratch) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const double w = wave_sum(v[i]);
+    if (lane == 0) scratch[wave * K + i] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    double tot = 0.0;
+    for (int w = 0; w < kWaves; ++w) tot += scratch[w * K + i];
+    v[i] = tot;
+  }
+  __syncthreads();  // the scratch is free again
+}
+
+// Payoff<Real>'s arithmetic (xs = x * s rounded to Real; df * max(. , 0) in Real), the put's mirror for
+// the call, each cast to f64 and added in f64.
+template <typename Real>
+__device__ __forceinline__ void price_add(const Payoff<Real>& pay, Real x, double (&v)[kPriceSums]) {
+  const Real xs = x * pay.s;
+  const Real dp = pay.K - xs, dc = xs - pay.K;
+  const double put = static_cast<double>(pay.df * (dp > Real(0) ? dp : Real(0)));
+  const double call = static_cast<double>(pay.df * (dc > Real(0) ? dc : Real(0)));
+  v[0] += put;
+  v[1] += call;
+  v[2] += static_cast<double>(xs);
+  v[3] += put * put;
+  v[4] += call * call;
+}
+
+template <typename Real, bool LOG_EULER, bool HW, int MODE>
+__global__ __launch_bounds__(kThreads) void price_kernel(EngineArgs a, double* __restrict__ prices) {
+  extern __shared__ double lds[];  // [kWaves][kPriceSums] scratch, then (kPriceLds) the parked terminal row
+  if constexpr (sizeof(Real) == 8) math::f64_tables_load();
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  const Contract c = load_contract(a.contracts + b * 6);
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+  const Stepper<Real, LOG_EULER, HW> step(c, T);
+  const Real x0 = static_cast<Real>(c.X0);
+  const PayoffPre<Real> pre(c);
+  Real* park = reinterpret_cast<Real*>(lds + kWaves * kPriceSums);
+
+  // the lane's 4 terminal values of one chunk; returns how many of them are paths (< P)
+  auto simulate = [&](int64_t chunk, Real (&xt)[kPathsPerLane]) {
+    const int64_t p0 = chunk + kPathsPerLane * static_cast<int64_t>(tid);
+    const int nvalid = static_cast<int>(p0 >= P ? 0 : (P - p0 >= kPathsPerLane ? kPathsPerLane : P - p0));
+    if (nvalid > 0) {
+      PathStream s(a.seed, ordinal, static_cast<uint64_t>(p0 / kPathsPerLane), T);
+      double unused = 0.0;
+      lane_rows_s<Real, LOG_EULER, HW, false, false>(s, step, x0, chunk, nullptr, T, 0, unused, xt, tid);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j) xt[j] = Real(0);
+    }
+    return nvalid;
+  };
+
+  double v[kPriceSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double sum[1] = {0.0};
+  Payoff<Real> pay;
+  if constexpr (MODE == kPriceRaw) pay = Payoff<Real>(a, pre, 1.0);  // a.normalize == 0: scale 1
+  for (int64_t chunk = 0; chunk < P; chunk += kChunk) {
+    Real xt[kPathsPerLane];
+    const int nvalid = simulate(chunk, xt);
+    Real part = 0;
+#pragma unroll
+    for (int j = 0; j < kPathsPerLane; ++j) part += j < nvalid ? xt[j] : Real(0);
+    sum[0] += static_cast<double>(part);
+    if constexpr (MODE == kPriceRaw) {
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j)
+        if (j < nvalid) price_add(pay, xt[j], v);
+    } else if constexpr (MODE == kPriceLds) {
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j)
+        if (j < nvalid) park[chunk + kPathsPerLane * tid + j] = xt[j];  // index < P: inside the parked row
+    }
+  }
+  price_reduce(sum, lds);
+  if constexpr (MODE != kPriceRaw) {
+    pay = Payoff<Real>(a, pre, sum[0]);
+    for (int64_t chunk = 0; chunk < P; chunk += kChunk) {
+      Real xt[kPathsPerLane];
+      int nvalid;
+      if constexpr (MODE == kPriceLds) {  // the lane's own values: no barrier needed
+        const int64_t p0 = chunk + kPathsPerLane * static_cast<int64_t>(tid);
+        nvalid = static_cast<int>(p0 >= P ? 0 : (P - p0 >= kPathsPerLane ? kPathsPerLane : P - p0));
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j) xt[j] = j < nvalid ? park[chunk + kPathsPerLane * tid + j] : Real(0);
+      } else {
+        nvalid = simulate(chunk, xt);
+      }
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j)
+        if (j < nvalid) price_add(pay, xt[j], v);
+    }
+  }
+  price_reduce(v, lds);
+  if (tid == 0) {
+    const double n = static_cast<double>(P);
+    const double put = v[0] / n, call = v[1] / n;
+    double put_se = 0.0, call_se = 0.0;
+    if (P > 1) {
+      const double pv = v[3] - n * put * put, cv = v[4] - n * call * call;
+      put_se = sqrt((pv > 0.0 ? pv : 0.0) / (n - 1.0) / n);
+      call_se = sqrt((cv > 0.0 ? cv : 0.0) / (n - 1.0) / n);
+    }
+    const Real ip = pre.K - pre.F, ic = pre.F - pre.K;
+    double* out = prices + b * SMC_PRICE_COLS;
+    out[0] = put;
+    out[1] = call;
+    out[2] = v[2] / n;
+    out[3] = put_se;
+    out[4] = call_se;
+    out[5] = static_cast<double>(pre.df * (ip > Real(0) ? ip : Real(0)));
+    out[6] = static_cast<double>(pre.df * (ic > Real(0) ? ic : Real(0)));
+    out[7] = sum[0];
+  }
+}
+
 template <typename Real, bool HW>
 __global__ __launch_bounds__(256) void normals_kernel(uint64_t seed, uint64_t ordinal, int32_t rows,
                                                       int64_t cols, Real* __restrict__ out) {
@@ -2087,6 +2243,51 @@ int32_t launch_engine(EngineArgs a, hipStream_t stream) {
   return fail(SMC_ERR_INVALID_ARGUMENT, "engine: unsupported scheme / math mode");
 }
 
+// price_kernel's mode and dynamic LDS for a shape (host only, no HIP call); -1: not a shape it takes
+int price_mode(int64_t P, int32_t scheme, int32_t normalization, int32_t dtype, size_t* lds) {
+  const size_t esz = dtype == SMC_DTYPE_F64 ? sizeof(double) : sizeof(float);
+  if (dtype != SMC_DTYPE_F32 && dtype != SMC_DTYPE_F64) return -1;
+  if ((scheme & SMC_MATH_REF) || ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)) return -1;
+  *lds = kPriceScratch;
+  if (normalization == SMC_NORM_RAW) return kPriceRaw;
+  if (scheme & SMC_PRICE_REPLAY) return kPriceReplay;
+  // P < 2^40 (validate_common); the f64 kernels also hold the static table image of the path math
+  const size_t park = kPriceScratch + ((static_cast<size_t>(P) * esz + 7) & ~size_t{7});
+  const size_t fixed = dtype == SMC_DTYPE_F64 ? sizeof(math::F64Tables) : 0;
+  if (park > kPriceParkBytes || park + fixed > kMaxLds) return kPriceReplay;
+  *lds = park;
+  return kPriceLds;
+}
+
+template <typename Real, bool LOG_EULER, bool HW>
+int32_t launch_price_k(const EngineArgs& a, int mode, size_t lds, double* prices, hipStream_t stream) {
+  auto kernel = mode == kPriceRaw   ? price_kernel<Real, LOG_EULER, HW, kPriceRaw>
+                : mode == kPriceLds ? price_kernel<Real, LOG_EULER, HW, kPriceLds>
+                                    : price_kernel<Real, LOG_EULER, HW, kPriceReplay>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "price_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kThreads), static_cast<uint32_t>(lds), stream, a, prices);
+  return check_launch("price_kernel");
+}
+
+template <typename Real>
+int32_t launch_price(const EngineArgs& a, int mode, size_t lds, double* prices, hipStream_t stream) {
+  const bool log_euler = (a.scheme & 0xff) == SMC_SCHEME_LOG_EULER;
+  const bool hw = (a.scheme & SMC_MATH_HW) != 0;
+  if constexpr (sizeof(Real) == 4) {
+    if (hw) {
+      return log_euler ? launch_price_k<Real, true, true>(a, mode, lds, prices, stream)
+                       : launch_price_k<Real, false, true>(a, mode, lds, prices, stream);
+    }
+  }
+  return log_euler ? launch_price_k<Real, true, false>(a, mode, lds, prices, stream)
+                   : launch_price_k<Real, false, false>(a, mode, lds, prices, stream);
+}
+
 __global__ void advance_cursor_kernel(int64_t* cursor, int64_t advance) {
   if (threadIdx.x == 0) {
     cursor[0] += advance;
@@ -2428,6 +2629,49 @@ int32_t smc_normals(uint64_t mc_seed, int64_t ordinal, int32_t rows, int64_t col
   else
     return fail(SMC_ERR_INVALID_ARGUMENT, "smc_normals: bad dtype");
   return check_launch("normals_kernel");
+}
+
+int32_t smc_gbm_price(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
+                      uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
+                      int32_t normalization, int32_t dtype, double* prices_dev, void* stream) {
+  if (int32_t st = validate_common(contracts_dev, n_contracts, timesteps, n_paths, dtype)) return st;
+  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price: prices_dev is NULL");
+  if (!valid_scheme(scheme & ~SMC_PRICE_REPLAY)) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price: bad scheme");
+  if (scheme & SMC_MATH_REF)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price: SMC_MATH_REF is for smc_train_targets / smc_train_step");
+  if ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price: SMC_MATH_HW is f32 only");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price: bad normalization");
+  if (n_contracts == 0) return SMC_OK;
+  size_t lds = 0;
+  const int mode = price_mode(n_paths, scheme, normalization, dtype, &lds);
+  EngineArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.scheme = scheme & ~SMC_PRICE_REPLAY;
+  a.normalize = normalization != SMC_NORM_RAW;
+  return dtype == SMC_DTYPE_F32 ? launch_price<float>(a, mode, lds, prices_dev, as_stream(stream))
+                                : launch_price<double>(a, mode, lds, prices_dev, as_stream(stream));
+}
+
+const char* smc_gbm_price_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                 int32_t dtype) {
+  size_t lds = 0;
+  if (timesteps <= 0 || n_paths <= 0 || n_paths >= (1LL << 40) || !valid_scheme(scheme & ~SMC_PRICE_REPLAY) ||
+      (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE))
+    return "unsupported";
+  switch (price_mode(n_paths, scheme, normalization, dtype, &lds)) {
+    case kPriceRaw: return "price_kernel(raw)";
+    case kPriceLds: return "price_kernel(lds)";
+    case kPriceReplay: return "price_kernel(replay)";
+    default: return "unsupported";
+  }
 }
 
 #pragma GCC visibility pop

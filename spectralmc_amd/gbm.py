@@ -3,6 +3,8 @@
 Public names and semantics follow the reference: ``SimulationParams`` /
 ``BlackScholesConfig`` + their ``build_*`` validators, and the single-GPU engine
 ``BlackScholes`` with ``_simulate`` -> ``price`` -> ``price_to_host`` and ``snapshot``.
+``price_batch`` / ``price_batch_device`` (not in the reference) price many contracts in one
+launch of the fused pricing kernel (``smc_gbm_price``).
 
 What changed underneath:
 * the normal matrix of contract m is not materialised: ``smc_gbm_simulate`` draws it in
@@ -18,7 +20,7 @@ What changed underneath:
 from __future__ import annotations
 
 from math import exp
-from typing import Annotated, Literal, TypeAlias
+from typing import Annotated, Literal, Sequence, TypeAlias
 
 import numpy as np
 import torch
@@ -168,6 +170,24 @@ class BlackScholes:
 
         model_config = ConfigDict(frozen=True, extra="forbid")
 
+    class BatchPrices(BaseModel):
+        """``smc_gbm_price``'s block for B contracts, column by column: ``[B]`` f64 device tensors."""
+
+        model_config = ConfigDict(arbitrary_types_allowed=True, extra="forbid")
+        put_price: torch.Tensor
+        call_price: torch.Tensor
+        underlying: torch.Tensor
+        put_stderr: torch.Tensor
+        call_stderr: torch.Tensor
+        put_price_intrinsic: torch.Tensor
+        call_price_intrinsic: torch.Tensor
+        terminal_sum: torch.Tensor
+
+    #: path math of price_batch / price_batch_device: "portable" (IEEE-only transcendentals, the draws and
+    #: arithmetic of price / price_to_host) or "hw" (hardware f32 transcendentals, float32 engines only:
+    #: throughput mode, within the f32 tolerance of "portable")
+    price_batch_math: str = "portable"
+
     def __init__(self, cfg: BlackScholesConfig) -> None:
         self._cfg = cfg
         self._sp = cfg.sim_params
@@ -266,6 +286,63 @@ class BlackScholes:
         if isinstance(res, Failure):
             return res
         return Success(self.get_host_price(res.value))
+
+    # ------------------------------------------------------------------ batched pricing
+    def _price_block(self, contracts: torch.Tensor) -> Result[torch.Tensor, NormalsError]:
+        """One ``smc_gbm_price`` launch on the current stream (no sync): the ``[B, 8]`` f64 block of
+        contracts ``[B, 6]`` f64 on the device; contract b takes ordinal ``ordinal + b``."""
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if contracts.ndim != 2 or contracts.shape[1] != len(FIELDS) or contracts.dtype != torch.float64:
+            raise ValueError(f"contracts must be a [B, {len(FIELDS)}] float64 tensor, got "
+                             f"{tuple(contracts.shape)} {contracts.dtype}")
+        _lib.require_device()
+        if not contracts.is_cuda:
+            raise ValueError("contracts must be a device tensor")
+        sp = self._sp
+        contracts = contracts.contiguous()
+        B = int(contracts.shape[0])
+        block = torch.empty((B, _lib.PRICE_COLS), dtype=torch.float64, device=contracts.device)
+        if self.price_batch_math not in ("portable", "hw"):
+            raise ValueError(f"price_batch_math must be 'portable' or 'hw', got {self.price_batch_math!r}")
+        scheme = scheme_code(self._cfg.path_scheme) | (_lib.MATH_HW if self.price_batch_math == "hw" else 0)
+        if B:
+            _lib.check(_lib.lib().smc_gbm_price(
+                _lib.ptr(contracts), B, sp.timesteps, sp.total_paths(), sp.mc_seed, None, self._served,
+                scheme, normalization_code(self._cfg.normalization), dtype_code(sp.dtype),
+                _lib.ptr(block), _lib.stream_handle()))
+            self._served += B
+        return Success(block)
+
+    def price_batch_device(self, contracts: torch.Tensor) -> Result["BlackScholes.BatchPrices", NormalsError]:
+        """Monte-Carlo prices of B contracts (``[B, 6]`` f64 device tensor, columns X0 K T r d v) in one
+        launch of the fused pricing kernel: no path matrix in memory, no host sync.  Consumes the
+        normal streams of B ``price`` calls (``snapshot`` reflects it)."""
+        res = self._price_block(contracts)
+        if isinstance(res, Failure):
+            return res
+        put, call, und, put_se, call_se, put_in, call_in, tsum = res.value.unbind(dim=1)
+        return Success(self.BatchPrices(put_price=put, call_price=call, underlying=und, put_stderr=put_se,
+                                        call_stderr=call_se, put_price_intrinsic=put_in,
+                                        call_price_intrinsic=call_in, terminal_sum=tsum))
+
+    def price_batch(self, inputs: "Sequence[BlackScholes.Inputs]"
+                    ) -> Result["list[BlackScholes.HostPricingResults]", NormalsError]:
+        """``[price_to_host(c) for c in inputs]`` as one launch and one device-to-host copy."""
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if len(inputs) == 0:
+            return Success([])
+        rows = [[float(getattr(c, f)) for f in FIELDS] for c in inputs]
+        res = self._price_block(torch.tensor(rows, dtype=torch.float64, device=self._device()))
+        if isinstance(res, Failure):
+            return res
+        out = []
+        for put, call, und, _, _, put_in, call_in, _ in res.value.cpu().tolist():
+            out.append(self.HostPricingResults(put_price_intrinsic=put_in, call_price_intrinsic=call_in,
+                                               underlying=und, put_convexity=put - put_in,
+                                               call_convexity=call - call_in, put_price=put, call_price=call))
+        return Success(out)
 
 
 def intrinsic_values(contract: "BlackScholes.Inputs") -> tuple[float, float, float]:
