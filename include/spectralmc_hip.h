@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 16  /* 14: smc_time_launches; 15: SMC_MATH_REF | SMC_MATH_HW; 16: smc_gbm_price */
+#define SMC_ABI_VERSION 17  /* 15: SMC_MATH_REF | SMC_MATH_HW; 16: smc_gbm_price; 17: smc_gbm_price_paths */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -395,6 +395,38 @@ int32_t smc_gbm_price(const double* contracts_dev, int64_t n_contracts, int32_t 
  * "price_kernel(replay)", or "unsupported".  Static string, no device call. */
 const char* smc_gbm_price_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
                                  int32_t dtype);
+
+/* ---- path-dependent batched pricing (ABI 17) --------------------------------
+ * Average-price (Asian), knock-out and fixed-strike lookback options beside the European pair, for B
+ * contracts in ONE launch and without a path matrix in memory: one workgroup per contract with the price
+ * call's streams, geometry and fixed sum order, so the block is bit-identical run to run and under any
+ * split of the batch.  The monitoring dates are the T grid points of the simulate call's matrix (X0 itself
+ * is not monitored).  Row t is seen as xs_t = x_t s_t rounded to the sim dtype: s_t = F_t / mean_p(x_t) under
+ * SMC_NORM_NORMALIZE (bit for bit the rows the simulate + normalize calls leave in memory, in portable
+ * math), xs_t = x_t under SMC_NORM_RAW.  Per path, in the sim dtype: avg = (sum_t xs_t) / T, mx = max_t xs_t,
+ * mn = min_t xs_t, ko = any_t (xs_t <= lower || xs_t >= upper); each payoff is df max(. , 0) in the sim dtype,
+ * cast to f64 and averaged over the P paths.  prices_dev [B][20]:
+ *    0 Asian put  (K - avg)            1 Asian call  (avg - K)
+ *    2 knock-out put (0 if ko, else K - xs_T)   3 knock-out call (0 if ko, else xs_T - K)
+ *    4 lookback put (K - mn)           5 lookback call (mx - K)
+ *    6 European put (K - xs_T)         7 European call (xs_T - K): the price call's columns 0 and 1
+ *    8..15 the standard errors of columns 0..7 (0 at P = 1)
+ *   16 mean of avg, 17 knocked share (count / P), 18 mean of mx, 19 mean of mn.
+ * barriers_dev [B][2] holds (lower, upper) per contract; NULL means no barrier (columns 2, 3 equal 6, 7 and
+ * column 17 is 0); a lower <= 0 or an upper of +inf switches that side off.  A knock-in is the European
+ * column minus the knock-out column.  RAW is one pass; NORMALIZE simulates twice (row sums, then payoffs;
+ * more often when T exceeds the 26 to 34 rows of per-lane f64 accumulators that fit in LDS).  scheme takes
+ * SMC_MATH_HW (f32 only); SMC_MATH_REF, SMC_TRAIN_DYNAMIC and SMC_PRICE_REPLAY are rejected, and so is
+ * (SMC_ERR_INVALID_SHAPE) a NORMALIZE run of more time steps than LDS holds row scales for (about 34,000
+ * in f32, 12,800 in f64).  Monitoring is discrete: no continuity correction; arithmetic averages only. */
+#define SMC_PATH_PRICE_COLS 20
+int32_t smc_gbm_price_paths(const double* contracts_dev /*[B][6]*/, const double* barriers_dev /*[B][2] or NULL*/,
+                            int64_t n_contracts, int32_t timesteps, int64_t n_paths, uint64_t mc_seed,
+                            const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme, int32_t normalization,
+                            int32_t dtype, double* prices_dev /*[B][20]*/, void* stream);
+/* "path_price_kernel(raw)", "path_price_kernel(replay)" or "unsupported".  Static string, no device call. */
+const char* smc_gbm_price_paths_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                       int32_t dtype);
 
 #ifdef __cplusplus
 }

@@ -42,7 +42,8 @@ STORE_ALL = 2
 SOBOL_BITS = 30
 PRICE_REPLAY = 0x800  # smc_gbm_price scheme flag: never park the terminal values in LDS
 PRICE_COLS = 8  # doubles per contract smc_gbm_price writes
-ABI_VERSION = 16
+PATH_PRICE_COLS = 20  # doubles per contract smc_gbm_price_paths writes
+ABI_VERSION = 17
 
 _c_i32, _c_i64, _c_u64, _c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
 
@@ -79,6 +80,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_gbm_price": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32,
                                _c_vp, _c_vp]),
     "smc_gbm_price_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
+    "smc_gbm_price_paths": (_c_i32, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32,
+                                     _c_i32, _c_vp, _c_vp]),
+    "smc_gbm_price_paths_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
     "smc_cvnn_plan": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_c_i64)]),
     "smc_cvnn_forward_backward": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64,
                                            _c_vp, _c_i64, _c_vp]),

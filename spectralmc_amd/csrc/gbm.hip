@@ -330,11 +330,17 @@ __device__ __forceinline__ void lane_paths(const EngineArgs& a, const Stepper<Re
 // a whole stream span, smc_rng.h).
 // stage (LDS, optional): the rows go there instead of to HBM, row r at stage + r * stage_stride + 4 lane_id
 // STORE = false (with !STORE_ALL, price_kernel): no row is written anywhere, the terminal values only go to x_out
-template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL, bool STORE = true>
+// hook (path_price_kernel): called as hook(x, t) after the step that makes row t, with the lane's 4 values of
+// that row in registers; T may then be a prefix of the stream's rows that ends on a step pair (an even row count).
+struct NoRowHook {
+  template <typename Real>
+  __device__ __forceinline__ void operator()(const Real (&)[kPathsPerLane], int) const {}
+};
+template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL, bool STORE = true, typename Hook = NoRowHook>
 __device__ __forceinline__ void lane_rows_s(PathStream& s, const Stepper<Real, LOG_EULER, HW>& step, Real x0,
                                             int64_t chunk, Real* contract_base, int T, int64_t pitch, double& acc,
                                             Real (&x_out)[kPathsPerLane], int lane_id, Real* stage = nullptr,
-                                            int stage_stride = 0);
+                                            int stage_stride = 0, Hook hook = Hook());
 
 template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL>
 __device__ __forceinline__ void lane_rows(const EngineArgs& a, const Stepper<Real, LOG_EULER, HW>& step, Real x0,
@@ -346,11 +352,11 @@ __device__ __forceinline__ void lane_rows(const EngineArgs& a, const Stepper<Rea
   lane_rows_s<Real, LOG_EULER, HW, STORE_ALL>(s, step, x0, chunk, contract_base, T, pitch, acc, x_out, lane_id);
 }
 
-template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL, bool STORE>
+template <typename Real, bool LOG_EULER, bool HW, bool STORE_ALL, bool STORE, typename Hook>
 __device__ __forceinline__ void lane_rows_s(PathStream& s, const Stepper<Real, LOG_EULER, HW>& step, Real x0,
                                             int64_t chunk, Real* contract_base, int T, int64_t pitch, double& acc,
                                             Real (&x_out)[kPathsPerLane], int lane_id, Real* stage,
-                                            int stage_stride) {
+                                            int stage_stride, Hook hook) {
   using V4 = typename Vec4T<Real>::type;
   constexpr bool kPacked = HW && LOG_EULER && sizeof(Real) == 4;
   constexpr bool kY64 = LOG_EULER && sizeof(Real) == 8;  // exponents drawn directly (lane_paths)
@@ -398,9 +404,11 @@ __device__ __forceinline__ void lane_rows_s(PathStream& s, const Stepper<Real, L
   for (int t = 0; t + 1 < T; t += 2) {
     draw();
     advance(zl);
+    hook(x, t);
     if constexpr (STORE_ALL) store();
     row += rstride;
     advance(zh);
+    hook(x, t + 1);
     if constexpr (STORE_ALL) store();
     row += rstride;
   }
@@ -409,6 +417,7 @@ __device__ __forceinline__ void lane_rows_s(PathStream& s, const Stepper<Real, L
     else if constexpr (kY64) s.f64_log_tail4(step.b, step.a, zl);
     else s.template normal_tail<HW>(zl);
     advance(zl);
+    hook(x, T - 1);
     if constexpr (STORE_ALL) store();
   }
   if constexpr (!STORE_ALL && STORE) store();
@@ -1836,6 +1845,218 @@ __global__ __launch_bounds__(kThreads) void price_kernel(EngineArgs a, double* _
   }
 }
 
+// ---- path-dependent batched pricing: path_price_kernel (smc_gbm_price_paths) --------------------
+// price_kernel's geometry, streams and sum order (one 512-lane workgroup per contract, 4 consecutive paths
+// per lane and 2048-path chunk, no row stored, lanes wholly past P idle), with a per-row hook on the rolled
+// path loop: every row t of the matrix smc_gbm_simulate + smc_gbm_normalize would leave in memory is seen in
+// registers as xs_t = x_t * s_t (rounded to Real; s_t = F_t / Real(rowsum_t / P) under NORMALIZE with
+// normalize_kernel's F_t, xs_t = x_t under RAW), and each path keeps its running sum, maximum, minimum and
+// a knocked flag (xs_t <= L || xs_t >= U at any row).  From those come eight payoffs per path in Payoff's
+// arithmetic (Asian, knock-out, fixed-strike lookback, European; put and call), and kPathSums f64 sums
+// per contract: the payoffs, their squares, the average, the knocked count, the maximum and the minimum.
+//   RAW        one pass.
+//   NORMALIZE  pass 1 gives all T row sums in simulate_contract<ALLROWS>'s order (the lane's valid values
+//              added left to right in Real from 0, then f64 per lane over its chunks, butterfly, waves
+//              0..7): the per-lane f64 accumulators of R rows live in dynamic LDS ([R][512] doubles, lane
+//              tid only ever touches column tid), and T > R rows are covered in sweeps of R rows, each
+//              re-simulating from row 0 up to its last row (R is even, so a sweep ends on a step pair or
+//              on row T - 1).  The T scales stay in LDS; pass 2 re-creates the same streams
+//              (kPriceReplay's way) and applies them.
+constexpr int kPathSums = 20;
+constexpr size_t kPathScratch = kWaves * kPathSums * sizeof(double);
+constexpr size_t kPathAccRow = kThreads * sizeof(double);  // one row of per-lane row-sum accumulators
+constexpr size_t kPathLdsBytes = 144 * 1024;               // dynamic LDS a workgroup may take (f32)
+
+// A uniform 64-bit value moved to a vector register pair: what path_price_kernel needs of its arguments only
+// after the path loops waits there, because the f64 path math leaves no scalar registers to spare.
+__device__ __forceinline__ uint64_t hold_in_vgprs(uint64_t u) {
+  const uint32_t lo = static_cast<uint32_t>(u), hi = static_cast<uint32_t>(u >> 32);
+  uint32_t vlo, vhi;
+  asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(vlo), "=&v"(vhi) : "s"(lo), "s"(hi));
+  return (static_cast<uint64_t>(vhi) << 32) | vlo;
+}
+template <typename P>
+__device__ __forceinline__ P* hold_in_vgprs(P* p) {
+  return reinterpret_cast<P*>(hold_in_vgprs(reinterpret_cast<uint64_t>(p)));
+}
+
+// F_t of normalize_kernel: times = linspace(dt, T, T) in f64, last point exact, the exp in the sim dtype
+template <typename Real>
+__device__ __forceinline__ Real row_forward(const Contract& c, int T, int t) {
+  const double dt = c.T / static_cast<double>(T);
+  const double step = T > 1 ? (c.T - dt) / static_cast<double>(T - 1) : 0.0;
+  const double t64 = (t == T - 1) ? c.T : dt + static_cast<double>(t) * step;
+  if constexpr (sizeof(Real) == 4)
+    return static_cast<float>(c.X0) * math::exp_any(static_cast<float>(c.r - c.d) * static_cast<float>(t64));
+  else
+    return c.X0 * exp((c.r - c.d) * t64);
+}
+
+template <typename Real, bool LOG_EULER, bool HW, bool NORMALIZE>
+__global__ __launch_bounds__(kThreads) void path_price_kernel(EngineArgs a, const double* __restrict__ barriers,
+                                                              double* __restrict__ prices, int sweep_rows) {
+  // [kWaves][kPathSums] scratch; NORMALIZE: then T scales (Real, padded to 8 B), then [sweep_rows][kThreads]
+  extern __shared__ double lds[];
+  if constexpr (sizeof(Real) == 8) math::f64_tables_load();
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  // what is needed of the arguments after the path loops waits in vector registers (hold_in_vgprs), and the
+  // chunk loops count in 32 bits against a per-lane path count
+  const double* const row = hold_in_vgprs(a.contracts + b * 6);
+  const double* const bar = hold_in_vgprs(barriers ? barriers + 2 * b : nullptr);
+  double* const out = hold_in_vgprs(prices + b * SMC_PATH_PRICE_COLS) + tid;  // column tid (< 20) of the block
+  const int nchunks = static_cast<int>((a.P + kChunk - 1) / kChunk);  // P < 2^40
+  const int64_t P = static_cast<int64_t>(hold_in_vgprs(static_cast<uint64_t>(a.P)));
+  const int64_t lane_left = P - kPathsPerLane * static_cast<int64_t>(tid);  // paths from the lane's first on
+  const Contract c = load_contract(row);
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+  const Stepper<Real, LOG_EULER, HW> step(c, T);
+  const Real x0 = static_cast<Real>(c.X0);
+  Real* scales = reinterpret_cast<Real*>(lds + kWaves * kPathSums);
+  double* acc = lds + kWaves * kPathSums + (static_cast<size_t>(T) * sizeof(Real) + 7) / 8;
+
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = lane_left - chunk;
+    return static_cast<int>(left <= 0 ? 0 : (left >= kPathsPerLane ? kPathsPerLane : left));
+  };
+
+  if constexpr (NORMALIZE) {
+    for (int t0 = 0; t0 < T; t0 += sweep_rows) {
+      const int nrows = T - t0 < sweep_rows ? T - t0 : sweep_rows;
+      for (int i = 0; i < nrows; ++i) acc[i * kThreads + tid] = 0.0;
+      for (int ci = 0; ci < nchunks; ++ci) {
+        const int64_t chunk = static_cast<int64_t>(ci) * kChunk;
+        const int nvalid = valid_paths(chunk);
+        if (nvalid > 0) {
+          PathStream s(a.seed, ordinal, static_cast<uint64_t>((chunk + kPathsPerLane * tid) / kPathsPerLane), T);
+          double unused = 0.0;
+          Real xt[kPathsPerLane];
+          lane_rows_s<Real, LOG_EULER, HW, false, false>(
+              s, step, x0, chunk, nullptr, t0 + nrows, 0, unused, xt, tid, nullptr, 0,
+              [&](const Real(&x)[kPathsPerLane], int t) {
+                if (t >= t0) {  // t < t0 + nrows <= T: row t - t0 of this sweep, the lane's own column
+                  Real part = 0;
+#pragma unroll
+                  for (int j = 0; j < kPathsPerLane; ++j) part += j < nvalid ? x[j] : Real(0);
+                  acc[(t - t0) * kThreads + tid] += static_cast<double>(part);
+                }
+              });
+        }
+      }
+      for (int i = 0; i < nrows; ++i) {
+        const double w = wave_sum(acc[i * kThreads + tid]);
+        if (lane == 0) acc[i * kThreads + tid] = w;  // the wave's sum, in its lane 0's own slot
+      }
+      __syncthreads();
+      if (tid < nrows) {
+        double tot = 0.0;
+        for (int w = 0; w < kWaves; ++w) tot += acc[tid * kThreads + w * 64];
+        scales[t0 + tid] = static_cast<Real>(tot / static_cast<double>(P));  // the row mean, for now
+      }
+      __syncthreads();  // the accumulators are free for the next sweep
+    }
+    // the contract row is read again where it is needed (here and for the payoff constants below), so its
+    // six doubles are not held in scalar registers across the path loops
+    const Contract cr = load_contract(row);
+    for (int t = tid; t < T; t += kThreads) scales[t] = row_forward<Real>(cr, T, t) / scales[t];
+    __syncthreads();
+  }
+
+  const PayoffPre<Real> pre(load_contract(row));
+  const Real K = pre.K, df = pre.df;
+  Real lower = -__builtin_huge_val(), upper = __builtin_huge_val();
+  if (bar) {
+    lower = static_cast<Real>(bar[0]);
+    upper = static_cast<Real>(bar[1]);
+  }
+  const Real steps = static_cast<Real>(T);
+  auto payoff = [&](Real diff) { return static_cast<double>(df * (diff > Real(0) ? diff : Real(0))); };
+  double v[kPathSums];
+#pragma unroll
+  for (int i = 0; i < kPathSums; ++i) v[i] = 0.0;
+  for (int ci = 0; ci < nchunks; ++ci) {
+    const int64_t chunk = static_cast<int64_t>(ci) * kChunk;
+    const int nvalid = valid_paths(chunk);
+    if (nvalid > 0) {
+      Real sa[kPathsPerLane], mx[kPathsPerLane], mn[kPathsPerLane], xt[kPathsPerLane];
+      unsigned knocked = 0;
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j) {
+        sa[j] = Real(0);
+        mx[j] = -__builtin_huge_val();
+        mn[j] = __builtin_huge_val();
+      }
+      PathStream s(a.seed, ordinal, static_cast<uint64_t>((chunk + kPathsPerLane * tid) / kPathsPerLane), T);
+      double unused = 0.0;
+      lane_rows_s<Real, LOG_EULER, HW, false, false>(
+          s, step, x0, chunk, nullptr, T, 0, unused, xt, tid, nullptr, 0, [&](const Real(&x)[kPathsPerLane], int t) {
+            Real sc = Real(1);
+            if constexpr (NORMALIZE) sc = scales[t];  // t < T
+#pragma unroll
+            for (int j = 0; j < kPathsPerLane; ++j) {
+              const Real xs = NORMALIZE ? x[j] * sc : x[j];
+              sa[j] += xs;
+              mx[j] = xs > mx[j] ? xs : mx[j];
+              mn[j] = xs < mn[j] ? xs : mn[j];
+              knocked |= (xs <= lower || xs >= upper) ? (1u << j) : 0u;
+            }
+          });
+      Real sc_last = Real(1);
+      if constexpr (NORMALIZE) sc_last = scales[T - 1];
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j) {
+        if (j < nvalid) {
+          const Real xs = NORMALIZE ? xt[j] * sc_last : xt[j];  // the hook's value of row T - 1
+          const Real avg = sa[j] / steps;
+          const bool ko = (knocked >> j) & 1u;
+          const double put = payoff(K - xs), call = payoff(xs - K);
+          const double pay[8] = {payoff(K - avg),   payoff(avg - K),   ko ? 0.0 : put, ko ? 0.0 : call,
+                                 payoff(K - mn[j]), payoff(mx[j] - K), put,            call};
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            v[i] += pay[i];
+            v[8 + i] += pay[i] * pay[i];
+          }
+          v[16] += static_cast<double>(avg);
+          v[17] += ko ? 1.0 : 0.0;
+          v[18] += static_cast<double>(mx[j]);
+          v[19] += static_cast<double>(mn[j]);
+        }
+      }
+    }
+  }
+  // price_reduce's order (wave butterfly, then waves 0..7), but sum i is totalled by thread i alone: every
+  // thread holding all kPathSums totals would take 8 * 20 LDS reads into registers
+  {
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < kPathSums; ++i) {
+      const double w = wave_sum(v[i]);
+      if (lane == 0) lds[wave * kPathSums + i] = w;
+    }
+  }
+  __syncthreads();
+  auto total = [&](int i) {
+    double tot = 0.0;
+    for (int w = 0; w < kWaves; ++w) tot += lds[w * kPathSums + i];
+    return tot;
+  };
+  const double n = static_cast<double>(P);
+  if (tid < 8) {  // a payoff's mean and standard error
+    const double m = total(tid) / n;
+    double se = 0.0;
+    if (P > 1) {
+      const double var = total(8 + tid) - n * m * m;
+      se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+    }
+    out[0] = m;
+    out[8] = se;
+  } else if (tid >= 16 && tid < kPathSums) {
+    out[0] = total(tid) / n;
+  }
+}
+
 template <typename Real, bool HW>
 __global__ __launch_bounds__(256) void normals_kernel(uint64_t seed, uint64_t ordinal, int32_t rows,
                                                       int64_t cols, Real* __restrict__ out) {
@@ -2288,6 +2509,56 @@ int32_t launch_price(const EngineArgs& a, int mode, size_t lds, double* prices, 
                    : launch_price_k<Real, false, false>(a, mode, lds, prices, stream);
 }
 
+// path_price_kernel's plan for a shape (host only, no HIP call): 0 one RAW pass, 1 the NORMALIZE replay, -1 not
+// a flag set it takes, -2 more time steps than LDS holds scales for.  NORMALIZE: *rows is the even number of
+// accumulator rows per sweep (T rounded up to even where that fits), *lds the dynamic LDS.
+int path_price_plan(int32_t T, int32_t scheme, int32_t normalization, int32_t dtype, size_t* lds, int* rows) {
+  if (dtype != SMC_DTYPE_F32 && dtype != SMC_DTYPE_F64) return -1;
+  if ((scheme & SMC_MATH_REF) || ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)) return -1;
+  *lds = kPathScratch;
+  *rows = 0;
+  if (normalization == SMC_NORM_RAW) return 0;
+  const size_t esz = dtype == SMC_DTYPE_F64 ? sizeof(double) : sizeof(float);
+  // the f64 kernels also hold the static table image of the path math
+  const size_t budget = dtype == SMC_DTYPE_F64 ? kMaxLds - sizeof(math::F64Tables) : kPathLdsBytes;
+  const size_t head = kPathScratch + ((static_cast<size_t>(T) * esz + 7) & ~size_t{7});
+  if (head + 2 * kPathAccRow > budget) return -2;
+  const size_t fit = ((budget - head) / kPathAccRow) & ~size_t{1};
+  const size_t want = (static_cast<size_t>(T) + 1) & ~size_t{1};
+  *rows = static_cast<int>(want < fit ? want : fit);
+  *lds = head + static_cast<size_t>(*rows) * kPathAccRow;
+  return 1;
+}
+
+template <typename Real, bool LOG_EULER, bool HW>
+int32_t launch_path_price_k(const EngineArgs& a, const double* barriers, size_t lds, int rows, double* prices,
+                            hipStream_t stream) {
+  auto kernel = a.normalize ? path_price_kernel<Real, LOG_EULER, HW, true> : path_price_kernel<Real, LOG_EULER, HW, false>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "path_price_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kThreads), static_cast<uint32_t>(lds), stream, a, barriers,
+         prices, rows);
+  return check_launch("path_price_kernel");
+}
+
+template <typename Real>
+int32_t launch_path_price(const EngineArgs& a, const double* barriers, size_t lds, int rows, double* prices,
+                          hipStream_t stream) {
+  const bool log_euler = (a.scheme & 0xff) == SMC_SCHEME_LOG_EULER;
+  if constexpr (sizeof(Real) == 4) {
+    if (a.scheme & SMC_MATH_HW) {
+      return log_euler ? launch_path_price_k<Real, true, true>(a, barriers, lds, rows, prices, stream)
+                       : launch_path_price_k<Real, false, true>(a, barriers, lds, rows, prices, stream);
+    }
+  }
+  return log_euler ? launch_path_price_k<Real, true, false>(a, barriers, lds, rows, prices, stream)
+                   : launch_path_price_k<Real, false, false>(a, barriers, lds, rows, prices, stream);
+}
+
 __global__ void advance_cursor_kernel(int64_t* cursor, int64_t advance) {
   if (threadIdx.x == 0) {
     cursor[0] += advance;
@@ -2670,6 +2941,54 @@ const char* smc_gbm_price_kernel(int32_t timesteps, int64_t n_paths, int32_t sch
     case kPriceRaw: return "price_kernel(raw)";
     case kPriceLds: return "price_kernel(lds)";
     case kPriceReplay: return "price_kernel(replay)";
+    default: return "unsupported";
+  }
+}
+
+int32_t smc_gbm_price_paths(const double* contracts_dev, const double* barriers_dev, int64_t n_contracts,
+                            int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                            int64_t ordinal0, int32_t scheme, int32_t normalization, int32_t dtype,
+                            double* prices_dev, void* stream) {
+  if (int32_t st = validate_common(contracts_dev, n_contracts, timesteps, n_paths, dtype)) return st;
+  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_paths: prices_dev is NULL");
+  if (!valid_scheme(scheme)) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_paths: bad scheme");
+  if (scheme & SMC_MATH_REF)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_gbm_price_paths: SMC_MATH_REF is for smc_train_targets / smc_train_step");
+  if ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_paths: SMC_MATH_HW is f32 only");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_paths: bad normalization");
+  size_t lds = 0;
+  int rows = 0;
+  if (path_price_plan(timesteps, scheme, normalization, dtype, &lds, &rows) < 0)
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_gbm_price_paths: timesteps beyond the row scales a workgroup's LDS holds");
+  if (n_contracts == 0) return SMC_OK;
+  EngineArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.scheme = scheme;
+  a.normalize = normalization != SMC_NORM_RAW;
+  return dtype == SMC_DTYPE_F32
+             ? launch_path_price<float>(a, barriers_dev, lds, rows, prices_dev, as_stream(stream))
+             : launch_path_price<double>(a, barriers_dev, lds, rows, prices_dev, as_stream(stream));
+}
+
+const char* smc_gbm_price_paths_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                       int32_t dtype) {
+  size_t lds = 0;
+  int rows = 0;
+  if (timesteps <= 0 || n_paths <= 0 || n_paths >= (1LL << 40) || !valid_scheme(scheme) ||
+      (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE))
+    return "unsupported";
+  switch (path_price_plan(timesteps, scheme, normalization, dtype, &lds, &rows)) {
+    case 0: return "path_price_kernel(raw)";
+    case 1: return "path_price_kernel(replay)";
     default: return "unsupported";
   }
 }

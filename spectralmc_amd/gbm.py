@@ -4,7 +4,9 @@ Public names and semantics follow the reference: ``SimulationParams`` /
 ``BlackScholesConfig`` + their ``build_*`` validators, and the single-GPU engine
 ``BlackScholes`` with ``_simulate`` -> ``price`` -> ``price_to_host`` and ``snapshot``.
 ``price_batch`` / ``price_batch_device`` (not in the reference) price many contracts in one
-launch of the fused pricing kernel (``smc_gbm_price``).
+launch of the fused pricing kernel (``smc_gbm_price``); ``price_paths_batch`` /
+``price_paths_batch_device`` do the same for the path-dependent payoffs (average-price, knock-out,
+fixed-strike lookback) monitored at the time grid (``smc_gbm_price_paths``).
 
 What changed underneath:
 * the normal matrix of contract m is not materialised: ``smc_gbm_simulate`` draws it in
@@ -183,7 +185,61 @@ class BlackScholes:
         call_price_intrinsic: torch.Tensor
         terminal_sum: torch.Tensor
 
-    #: path math of price_batch / price_batch_device: "portable" (IEEE-only transcendentals, the draws and
+    class PathBatchPrices(BaseModel):
+        """``smc_gbm_price_paths``' block for B contracts, column by column: ``[B]`` f64 device tensors."""
+
+        model_config = ConfigDict(arbitrary_types_allowed=True, extra="forbid")
+        asian_put: torch.Tensor
+        asian_call: torch.Tensor
+        knock_out_put: torch.Tensor
+        knock_out_call: torch.Tensor
+        lookback_put: torch.Tensor
+        lookback_call: torch.Tensor
+        put_price: torch.Tensor
+        call_price: torch.Tensor
+        asian_put_stderr: torch.Tensor
+        asian_call_stderr: torch.Tensor
+        knock_out_put_stderr: torch.Tensor
+        knock_out_call_stderr: torch.Tensor
+        lookback_put_stderr: torch.Tensor
+        lookback_call_stderr: torch.Tensor
+        put_price_stderr: torch.Tensor
+        call_price_stderr: torch.Tensor
+        mean_average: torch.Tensor
+        knocked_share: torch.Tensor
+        mean_max: torch.Tensor
+        mean_min: torch.Tensor
+
+    class HostPathPrices(BaseModel):
+        """One contract's row of ``PathBatchPrices`` on the host, with the knock-in prices (the European
+        price minus the knock-out price)."""
+
+        asian_put: float
+        asian_call: float
+        knock_out_put: float
+        knock_out_call: float
+        lookback_put: float
+        lookback_call: float
+        put_price: float
+        call_price: float
+        asian_put_stderr: float
+        asian_call_stderr: float
+        knock_out_put_stderr: float
+        knock_out_call_stderr: float
+        lookback_put_stderr: float
+        lookback_call_stderr: float
+        put_price_stderr: float
+        call_price_stderr: float
+        mean_average: float
+        knocked_share: float
+        mean_max: float
+        mean_min: float
+        knock_in_put: float
+        knock_in_call: float
+
+        model_config = ConfigDict(frozen=True, extra="forbid")
+
+    #: path math of price_batch / price_batch_device and of price_paths_batch / price_paths_batch_device: "portable" (IEEE-only transcendentals, the draws and
     #: arithmetic of price / price_to_host) or "hw" (hardware f32 transcendentals, float32 engines only:
     #: throughput mode, within the f32 tolerance of "portable")
     price_batch_math: str = "portable"
@@ -342,6 +398,82 @@ class BlackScholes:
             out.append(self.HostPricingResults(put_price_intrinsic=put_in, call_price_intrinsic=call_in,
                                                underlying=und, put_convexity=put - put_in,
                                                call_convexity=call - call_in, put_price=put, call_price=call))
+        return Success(out)
+
+    # ------------------------------------------------------------------ batched path-dependent pricing
+    def _path_price_block(self, contracts: torch.Tensor, barriers: torch.Tensor | None
+                          ) -> Result[torch.Tensor, NormalsError]:
+        """One ``smc_gbm_price_paths`` launch on the current stream (no sync): the ``[B, 20]`` f64 block of
+        contracts ``[B, 6]`` (and barriers ``[B, 2]`` or None) f64 on the device; contract b takes ordinal
+        ``ordinal + b``."""
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        for name, t, cols in (("contracts", contracts, len(FIELDS)), ("barriers", barriers, 2)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.ndim != 2 or t.shape[1] != cols or t.dtype != torch.float64:
+                raise ValueError(f"{name} must be a [B, {cols}] float64 tensor, got "
+                                 f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+        if barriers is not None and barriers.shape[0] != contracts.shape[0]:
+            raise ValueError(f"barriers must have one (lower, upper) row per contract: {barriers.shape[0]} rows "
+                             f"for {contracts.shape[0]} contracts")
+        _lib.require_device()
+        if not contracts.is_cuda or (barriers is not None and barriers.device != contracts.device):
+            raise ValueError("contracts and barriers must be tensors on the same device")
+        if self.price_batch_math not in ("portable", "hw"):
+            raise ValueError(f"price_batch_math must be 'portable' or 'hw', got {self.price_batch_math!r}")
+        sp = self._sp
+        contracts = contracts.contiguous()
+        barriers = None if barriers is None else barriers.contiguous()
+        B = int(contracts.shape[0])
+        block = torch.empty((B, _lib.PATH_PRICE_COLS), dtype=torch.float64, device=contracts.device)
+        scheme = scheme_code(self._cfg.path_scheme) | (_lib.MATH_HW if self.price_batch_math == "hw" else 0)
+        if B:
+            _lib.check(_lib.lib().smc_gbm_price_paths(
+                _lib.ptr(contracts), _lib.ptr(barriers), B, sp.timesteps, sp.total_paths(), sp.mc_seed, None,
+                self._served, scheme, normalization_code(self._cfg.normalization), dtype_code(sp.dtype),
+                _lib.ptr(block), _lib.stream_handle()))
+            self._served += B
+        return Success(block)
+
+    def price_paths_batch_device(self, contracts: torch.Tensor, barriers: torch.Tensor | None = None
+                                 ) -> Result["BlackScholes.PathBatchPrices", NormalsError]:
+        """Path-dependent Monte-Carlo prices of B contracts (``[B, 6]`` f64 device tensor, columns X0 K T r d v)
+        in one launch of the fused kernel, with no path matrix in memory and no host sync: average-price
+        (Asian), knock-out and fixed-strike lookback puts and calls beside the European pair, monitored at
+        the engine's ``timesteps`` grid points.  ``barriers`` is a ``[B, 2]`` f64 device tensor of
+        (lower, upper) per contract, or None for no barrier.  Consumes the normal streams of B ``price``
+        calls (``snapshot`` reflects it)."""
+        res = self._path_price_block(contracts, barriers)
+        if isinstance(res, Failure):
+            return res
+        return Success(self.PathBatchPrices(**dict(zip(self.PathBatchPrices.model_fields, res.value.unbind(dim=1)))))
+
+    def price_paths_batch(self, inputs: "Sequence[BlackScholes.Inputs]",
+                          barriers: "Sequence[tuple[float, float]] | None" = None
+                          ) -> Result["list[BlackScholes.HostPathPrices]", NormalsError]:
+        """``price_paths_batch_device`` from host values: one launch and one device-to-host copy.
+        ``barriers`` is one (lower, upper) pair per contract, or None."""
+        if barriers is not None and len(barriers) != len(inputs):
+            raise ValueError(f"barriers must have one (lower, upper) pair per contract: {len(barriers)} pairs "
+                             f"for {len(inputs)} contracts")
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if len(inputs) == 0:
+            return Success([])
+        dev = self._device()
+        rows = [[float(getattr(c, f)) for f in FIELDS] for c in inputs]
+        bars = None if barriers is None else torch.tensor([[float(lo), float(up)] for lo, up in barriers],
+                                                          dtype=torch.float64, device=dev)
+        res = self._path_price_block(torch.tensor(rows, dtype=torch.float64, device=dev), bars)
+        if isinstance(res, Failure):
+            return res
+        names = list(self.PathBatchPrices.model_fields)
+        out = []
+        for row in res.value.cpu().tolist():
+            cols = dict(zip(names, row))
+            out.append(self.HostPathPrices(knock_in_put=cols["put_price"] - cols["knock_out_put"],
+                                           knock_in_call=cols["call_price"] - cols["knock_out_call"], **cols))
         return Success(out)
 
 
