@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 17  /* 15: SMC_MATH_REF | SMC_MATH_HW; 16: smc_gbm_price; 17: smc_gbm_price_paths */
+#define SMC_ABI_VERSION 18  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -427,6 +427,47 @@ int32_t smc_gbm_price_paths(const double* contracts_dev /*[B][6]*/, const double
 /* "path_price_kernel(raw)", "path_price_kernel(replay)" or "unsupported".  Static string, no device call. */
 const char* smc_gbm_price_paths_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
                                        int32_t dtype);
+
+/* ---- batched basket pricing (ABI 18) ------------------------------------------
+ * Monte-Carlo prices of the equal-weight basket and of the two rainbow payoffs (best-of, worst-of) on the
+ * correlated multi-asset engine, for B contracts in ONE launch and without a terminal buffer in memory: one
+ * workgroup per contract with smc_basket_train_targets' contract rows ([B][3A+4]: K, T, r, rho, X0[A], d[A],
+ * v[A]), streams (contract b uses ordinal (*ordinal_dev or 0) + ordinal0 + b), Cholesky and packed f32 step;
+ * the A terminal values of a path stay in registers.  Unlike the training call any n_paths >= 1 is taken.
+ * Per path, all in f32 (the engine's only dtype; the training targets' payoff arithmetic):
+ *   xs_i = x_i s_i, s_i = F_i / f32(tot_i / P) under SMC_NORM_NORMALIZE (F_i = f32(X0_i) exp(f32(r - d_i) f32(T)),
+ *   tot_i the f64 sum of asset i's raw terminal values), s_i = 1 under SMC_NORM_RAW;
+ *   bk = (((0 + xs_0) + xs_1) + ...) f32(1 / A), mx = max_i xs_i, mn = min_i xs_i;
+ *   each payoff is df max(. , 0) with df = exp(f32(-r) f32(T)), cast to f64 and averaged over the P paths.
+ * prices_dev [B][18]:
+ *    0 basket put    (K - bk)            1 basket call    (bk - K)
+ *    2 best-of put   (K - mx)            3 best-of call   (mx - K)
+ *    4 worst-of put  (K - mn)            5 worst-of call  (mn - K)
+ *    6..11 the standard errors of columns 0..5 (0 at P = 1)
+ *   12 mean of bk, 13 mean of mx, 14 mean of mn, 15 exercise share of the basket put (count(bk < K) / P)
+ *   16 / 17 intrinsic basket put / call df max(K - Fb, 0) / df max(Fb - K, 0), Fb = (((0 + F_0) + F_1) + ...) f32(1 / A).
+ * terminal_sum_dev (may be NULL): [B][A] f64, the tot_i (smc_basket_train_targets' terminal sums bit for bit
+ * where n_paths is a multiple of 2048).  Every sum has one fixed order: the block is bit-identical run to run,
+ * under any split of the batch and whichever way the kernel keeps the terminal values (NORMALIZE needs them
+ * twice: parked in LDS while A * roundup4(P) * 4 bytes and 2112 bytes of scratch fit in 144 KiB, else simulated
+ * a second time; SMC_PRICE_REPLAY forces the latter).  math: 0 (portable, CPU-reproducible) or SMC_MATH_HW,
+ * optionally | SMC_PRICE_REPLAY; any other bit (SMC_MATH_REF, SMC_TRAIN_DYNAMIC, ...) is rejected.
+ * SMC_ERR_INVALID_ARGUMENT: NULL contracts_dev / prices_dev, n_assets outside 1..8, bad math, bad
+ * normalization.  SMC_ERR_INVALID_SHAPE: n_contracts < 0 or >= 2^31, timesteps <= 0, n_paths <= 0 or >= 2^40.
+ * All of these are reported before the empty batch (n_contracts = 0: SMC_OK, nothing touched) is accepted.
+ * Contract values are not validated on the device, as in the engine: an indefinite correlation matrix
+ * (rho <= -1 / (A - 1)) gives NaN, and rho = 1 is only meaningful for A <= 2 (from A = 3 on the
+ * Banachiewicz factorisation divides 0 by 0).  B below the CU count leaves CUs idle (a contract is not split
+ * over workgroups).  Equal weights and equicorrelation only; no path-dependent basket payoffs. */
+#define SMC_BASKET_PRICE_COLS 18
+int32_t smc_basket_price(const double* contracts_dev /*[B][3A+4]*/, int64_t n_contracts, int32_t n_assets,
+                         int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                         int64_t ordinal0, int32_t math, int32_t normalization,
+                         double* prices_dev /*[B][18]*/, double* terminal_sum_dev /*[B][A] or NULL*/, void* stream);
+/* "basket_price_kernel(raw)", "basket_price_kernel(lds)", "basket_price_kernel(replay)" or "unsupported" (a
+ * call smc_basket_price rejects).  Static string, no device call. */
+const char* smc_basket_price_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                    int32_t normalization);
 
 #ifdef __cplusplus
 }

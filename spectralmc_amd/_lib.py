@@ -43,7 +43,8 @@ SOBOL_BITS = 30
 PRICE_REPLAY = 0x800  # smc_gbm_price scheme flag: never park the terminal values in LDS
 PRICE_COLS = 8  # doubles per contract smc_gbm_price writes
 PATH_PRICE_COLS = 20  # doubles per contract smc_gbm_price_paths writes
-ABI_VERSION = 17
+BASKET_PRICE_COLS = 18  # doubles per contract smc_basket_price writes
+ABI_VERSION = 18
 
 _c_i32, _c_i64, _c_u64, _c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
 
@@ -99,6 +100,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_basket_sync_bytes": (_c_i64, [_c_i32, _c_i32, _c_i32, _c_i32, _c_i64]),
     "smc_basket_train_targets_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32]),
     "smc_basket_resident_slots": (_c_i64, [_c_i32, _c_i32, _c_i32]),
+    "smc_basket_price": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
+                                  _c_vp, _c_vp]),
+    "smc_basket_price_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i32]),
 }
 
 # include/spectralmc_hip_testing.h: test-only entry points, inert unless SMC_ENABLE_TEST_HOOKS=1

@@ -17,7 +17,9 @@ per chunk of contracts, after the Sobol draw; no host synchronisation.
 3A+4 inputs trains on baskets through ``use_basket_engine``.  Snapshots of such a pricer
 record the network, optimizer and Sobol/normal positions as usual but not the basket
 configuration: call ``use_basket_engine`` again on the restored pricer.  ``predict_price``
-stays single-asset (the reference has no basket pricing API).
+stays single-asset; the Monte-Carlo price of a basket (and of the best-of / worst-of payoffs on the
+same paths) comes from ``basket_price`` / ``BasketEngine.price``: one launch of ``smc_basket_price`` for
+B contracts, no terminal buffer in memory.
 """
 
 from __future__ import annotations
@@ -147,6 +149,66 @@ def basket_targets(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int 
     return targets
 
 
+PRICE_FIELDS = ("basket_put", "basket_call", "best_of_put", "best_of_call", "worst_of_put", "worst_of_call",
+                "basket_put_stderr", "basket_call_stderr", "best_of_put_stderr", "best_of_call_stderr",
+                "worst_of_put_stderr", "worst_of_call_stderr", "mean_basket", "mean_best", "mean_worst",
+                "put_exercise_share", "basket_put_intrinsic", "basket_call_intrinsic")
+
+
+@dataclass(frozen=True)
+class BasketPrices:
+    """``smc_basket_price``'s block for B contracts: one [B] f64 device tensor per column (views of
+    ``block`` [B, 18], in ``PRICE_FIELDS`` order) and the raw terminal sums ``terminal_sum`` [B, A]."""
+    basket_put: torch.Tensor
+    basket_call: torch.Tensor
+    best_of_put: torch.Tensor
+    best_of_call: torch.Tensor
+    worst_of_put: torch.Tensor
+    worst_of_call: torch.Tensor
+    basket_put_stderr: torch.Tensor
+    basket_call_stderr: torch.Tensor
+    best_of_put_stderr: torch.Tensor
+    best_of_call_stderr: torch.Tensor
+    worst_of_put_stderr: torch.Tensor
+    worst_of_call_stderr: torch.Tensor
+    mean_basket: torch.Tensor
+    mean_best: torch.Tensor
+    mean_worst: torch.Tensor
+    put_exercise_share: torch.Tensor
+    basket_put_intrinsic: torch.Tensor
+    basket_call_intrinsic: torch.Tensor
+    terminal_sum: torch.Tensor
+    block: torch.Tensor
+
+
+def basket_price(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 0, n_paths: int | None = None,
+                 replay: bool = False) -> BasketPrices:
+    """Monte-Carlo prices of the basket, best-of and worst-of puts and calls of device contracts [B, 3A+4]
+    f64: one launch of ``smc_basket_price`` on the current stream, no host synchronisation.  ``cfg`` gives
+    n_assets, timesteps, mc_seed, normalize and math; ``n_paths`` (default ``cfg.total_paths``) may be any
+    positive count.  ``replay``: never park the terminal values in LDS (the same bits, for timing)."""
+    if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
+            not contracts.is_contiguous():
+        raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
+    P = cfg.total_paths if n_paths is None else int(n_paths)
+    if P <= 0:
+        raise ValueError(f"n_paths must be positive, got {n_paths}")
+    _lib.require_device()
+    if not contracts.is_cuda:
+        raise ValueError("contracts must be a device tensor")
+    B = contracts.shape[0]
+    block = torch.empty((B, _lib.BASKET_PRICE_COLS), dtype=torch.float64, device=contracts.device)
+    tsum = torch.empty((B, cfg.n_assets), dtype=torch.float64, device=contracts.device)
+    if B > 0:
+        math = (_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0)
+        _lib.check(_lib.lib().smc_basket_price(
+            _lib.ptr(contracts), B, cfg.n_assets, cfg.timesteps, P, cfg.mc_seed, None, ordinal0, math,
+            _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW, _lib.ptr(block), _lib.ptr(tsum),
+            _lib.stream_handle()))
+    return BasketPrices(**{name: block[:, col] for col, name in enumerate(PRICE_FIELDS)}, terminal_sum=tsum,
+                        block=block)
+
+
 class BasketEngine:
     """Device buffers + launches of the basket Monte-Carlo side of one training step
     (the ``TrainingEngine`` interface)."""
@@ -251,6 +313,13 @@ class BasketEngine:
             self.chunk, _lib.ptr(self.terminal_sum), _lib.ptr(b.targets), _lib.ptr(self._sync), self._sync_bytes,
             stream))
 
+    def price(self, contracts: torch.Tensor | None = None, *, ordinal0: int = 0,
+              n_paths: int | None = None) -> BasketPrices:
+        """Monte-Carlo prices (``basket_price``) with the engine's configuration, by default of the contracts
+        of the last enqueued step: the Monte-Carlo side of checking a basket-trained network."""
+        return basket_price(self.buffers.contracts if contracts is None else contracts, self.cfg, ordinal0=ordinal0,
+                            n_paths=n_paths)
+
 
 def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) -> None:
     """Make ``pricer`` train on basket contracts: its training sessions build a ``BasketEngine``
@@ -262,5 +331,5 @@ def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) ->
     pricer.mc_engine_factory = factory
 
 
-__all__ = ["BasketConfig", "BasketEngine", "basket_fields", "basket_targets", "default_basket_bounds",
-           "use_basket_engine", "MAX_ASSETS"]
+__all__ = ["BasketConfig", "BasketEngine", "BasketPrices", "basket_fields", "basket_price", "basket_targets",
+           "default_basket_bounds", "use_basket_engine", "MAX_ASSETS"]

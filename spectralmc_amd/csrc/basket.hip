@@ -16,6 +16,8 @@
 // contract; each lane owns 4 consecutive paths of a 2048-path chunk for all A assets and stores
 // one dwordx4 per (asset, row).  basket_resident_kernel (the C5 kernel, below): W = P / 4096
 // co-resident 1024-thread workgroups per contract keep the terminal rows on chip.
+// basket_price_kernel (smc_basket_price): basket_kernel's geometry with no row stored; the equal-weight
+// basket, best-of and worst-of prices of a contract leave as 18 doubles.
 //
 // Per lane, per step t, per path j = 0..3: ceil(A/2) Box-Muller pairs from the lane's
 // PathStream (smc_rng.h; the same (seed, contract ordinal, group) keying as the single-asset
@@ -297,6 +299,252 @@ __global__ __launch_bounds__(kBThreads) void basket_cf_kernel(BasketArgs a) {
   if (threadIdx.x < A) tot[threadIdx.x] = a.terminal_sum[b * A + threadIdx.x];
   __syncthreads();
   basket_cf<A>(a, b, tot, part, avg, cs, sn);
+}
+
+// ---- batched basket pricing: basket_price_kernel (smc_basket_price) ------------------------------
+// basket_kernel's geometry, streams and step (one 512-lane workgroup per contract, 4 consecutive paths
+// of every 2048-path chunk per lane for all A assets, PathStream(seed, ordinal, chunk / 4 + tid), draws
+// in path pairs, the packed f32 step), with no row stored: the A scaled terminal values of a path are
+// seen in registers, xs_i = x_i s_i with basket_cf's scale s_i = F_i / f32(tot_i / P) (1 under RAW), and
+// give the equal-weight basket bk = (((0 + xs_0) + xs_1) + ...) f32(1 / A), the best mx = max_i xs_i and
+// the worst mn = min_i xs_i.  Six payoffs per path (put and call on each, df max(. , 0) in f32, cast to
+// f64) and kBPriceSums f64 sums per contract: the payoffs, their squares, bk, mx, mn and the count of
+// paths with bk < K.  Any P >= 1: a lane whose 4 paths lie wholly past P neither draws nor contributes,
+// one with 1 to 3 paths draws for all 4 (the stream is per group of 4) and counts the valid ones.
+// Terminal sums: the lane's valid values left to right in f32 from 0, then f64 per lane over its chunks,
+// wave butterfly, waves 0..7 (basket_kernel's order, bit for bit where 2048 | P).  Payoff sums: per lane
+// over its chunks and paths in order, wave butterfly, waves 0..7, sum i totalled by thread i.
+//   kBPriceRaw     RAW normalisation: one pass, the payoffs taken as the paths finish;
+//   kBPriceLds     NORMALIZE: each lane parks its terminal values in dynamic LDS ([A][P rounded up to 4]
+//                  f32, one 16-B slot per lane, chunk and asset; a lane reads back only what it wrote)
+//                  and takes the payoffs from there once the A sums are known;
+//   kBPriceReplay  NORMALIZE, the parked block too large (or SMC_PRICE_REPLAY): pass 1 gives the sums,
+//                  pass 2 re-creates the same streams: kBPriceLds' values and order, so the same bits.
+// Contract values are not validated: an indefinite correlation matrix gives NaN, and rho = 1 is only
+// meaningful for A <= 2 (from A = 3 on the factorisation divides 0 by 0).
+enum BasketPriceMode : int { kBPriceRaw = 0, kBPriceLds = 1, kBPriceReplay = 2 };
+constexpr int kBPriceSums = 16;  // 6 payoffs, their squares, bk, mx, mn, count(bk < K)
+// scratch at the head of the dynamic LDS: payoff-sum partials [kBWaves][kBPriceSums], the Cholesky factor
+// [8][8], terminal-sum partials [kBWaves][8] and totals [8] (f64; 2112 B, a multiple of 16)
+constexpr int kBPriceHead = kBWaves * kBPriceSums + kMaxAssets * kMaxAssets + kBWaves * kMaxAssets + kMaxAssets;
+constexpr size_t kBPriceScratch = kBPriceHead * sizeof(double);
+// Largest dynamic LDS (scratch + parked block) of the lds mode: price_kernel's bound (gbm.hip)
+#ifndef SMC_PRICE_PARK_BYTES
+#define SMC_PRICE_PARK_BYTES (144 * 1024)
+#endif
+constexpr size_t kBPriceParkBytes = SMC_PRICE_PARK_BYTES;
+
+// The lane's 4 paths of all A assets of one chunk from x0 through the T steps: basket_kernel's path loop
+// without its row stores (the same draws and packed f32 ops in the same order).
+template <int A, bool HW>
+__device__ __forceinline__ void basket_lane_paths(PathStream& s, const float (&ca)[A], const float (&x0)[A],
+                                                  const float (&Lb)[A][A], int T, float (&x)[A][kBPaths]) {
+  typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int i = 0; i < A; ++i)
+#pragma unroll
+    for (int j = 0; j < kBPaths; ++j) x[i][j] = x0[i];
+  for (int t = 0; t < T; ++t) {
+#pragma unroll
+    for (int j = 0; j < kBPaths; j += 2) {
+      float z0[A + 1], z1[A + 1];
+#pragma unroll
+      for (int k = 0; k < A; k += 2) s.template normal_pair<HW>(z0[k], z0[k + 1]);
+#pragma unroll
+      for (int k = 0; k < A; k += 2) s.template normal_pair<HW>(z1[k], z1[k + 1]);
+#pragma unroll
+      for (int i = 0; i < A; ++i) {
+        f2 y = {ca[i], ca[i]};
+#pragma unroll
+        for (int k = 0; k <= i; ++k) y = __builtin_elementwise_fma(f2{Lb[i][k], Lb[i][k]}, f2{z0[k], z1[k]}, y);
+        f2 e;
+        if constexpr (HW) e = f2{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
+        else e = f2{math::exp2_any(y.x), math::exp2_any(y.y)};
+        const f2 xv = f2{x[i][j], x[i][j + 1]} * e;
+        x[i][j] = xv.x;
+        x[i][j + 1] = xv.y;
+      }
+    }
+  }
+}
+
+template <int A, bool HW, int MODE>
+__global__ __launch_bounds__(kBThreads) void basket_price_kernel(BasketArgs a, double* __restrict__ prices) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  extern __shared__ double lds[];  // kBPriceHead doubles of scratch, then (kBPriceLds) the parked block
+  double* Ld = lds + kBWaves * kBPriceSums;     // [8][8]
+  double* wsum = Ld + kMaxAssets * kMaxAssets;  // [kBWaves][A]
+  double* tot = wsum + kBWaves * kMaxAssets;    // [A]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  const int64_t P4 = (P + 3) & ~int64_t{3};  // the parked block's row length
+  v4f* park = reinterpret_cast<v4f*>(lds + kBPriceHead);
+
+  const double* c = a.contracts + b * (3 * A + 4);
+  const double Tm = c[1], r = c[2], rho = c[3];
+  if (tid == 0) cholesky_equicorr(A, rho, Ld);
+  __syncthreads();
+  // per-asset log2-unit coefficients, as basket_kernel
+  const double dt = Tm / static_cast<double>(T);
+  const double sq = sqrt(dt);
+  constexpr double zscale = HW ? PathStream::kNormalScale<true> : 1.0;
+  float ca[A], x0[A], Lb[A][A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double drift = r - d - 0.5 * v * v;
+    ca[i] = static_cast<float>(drift * dt * kBLog2e);
+    const double bi = v * sq * kBLog2e * zscale;
+    x0[i] = static_cast<float>(c[4 + i]);
+#pragma unroll
+    for (int k = 0; k < A; ++k) Lb[i][k] = k <= i ? static_cast<float>(bi * Ld[i * kMaxAssets + k]) : 0.0f;
+  }
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+
+  // payoff constants (basket_cf's arithmetic)
+  const float Tf = static_cast<float>(Tm);
+  const float df = math::exp_any(static_cast<float>(-r) * Tf);
+  const float Kf = static_cast<float>(c[0]);
+  const float wA = static_cast<float>(1.0 / A);
+  auto forward = [&](int i) {
+    return static_cast<float>(c[4 + i]) * math::exp_any(static_cast<float>(r - c[4 + A + i]) * Tf);
+  };
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = P - chunk - kBPaths * static_cast<int64_t>(tid);
+    return static_cast<int>(left <= 0 ? 0 : (left >= kBPaths ? kBPaths : left));
+  };
+  auto simulate = [&](int64_t chunk, float(&x)[A][kBPaths]) {
+    PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+    basket_lane_paths<A, HW>(s, ca, x0, Lb, T, x);
+  };
+  double v[kBPriceSums];
+#pragma unroll
+  for (int i = 0; i < kBPriceSums; ++i) v[i] = 0.0;
+  auto payoffs = [&](const float(&x)[A][kBPaths], int nvalid, const float(&sc)[A]) {
+    auto pay = [&](float diff) { return static_cast<double>(df * (diff > 0.0f ? diff : 0.0f)); };
+#pragma unroll
+    for (int j = 0; j < kBPaths; ++j) {
+      if (j < nvalid) {
+        float bs = 0.0f, mx = 0.0f, mn = 0.0f;
+#pragma unroll
+        for (int i = 0; i < A; ++i) {
+          const float xs = x[i][j] * sc[i];
+          bs = bs + xs;
+          mx = i == 0 || xs > mx ? xs : mx;
+          mn = i == 0 || xs < mn ? xs : mn;
+        }
+        const float bk = bs * wA;
+        const double p[6] = {pay(Kf - bk), pay(bk - Kf), pay(Kf - mx), pay(mx - Kf), pay(Kf - mn), pay(mn - Kf)};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          v[i] += p[i];
+          v[6 + i] += p[i] * p[i];
+        }
+        v[12] += static_cast<double>(bk);
+        v[13] += static_cast<double>(mx);
+        v[14] += static_cast<double>(mn);
+        v[15] += bk < Kf ? 1.0 : 0.0;
+      }
+    }
+  };
+
+  // pass 1: the terminal sums (RAW: and the payoffs, scale 1; lds: and the parked values)
+  float sc[A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) sc[i] = 1.0f;
+  double acc[A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) acc[i] = 0.0;
+  for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+    const int nvalid = valid_paths(chunk);
+    if (nvalid > 0) {
+      float x[A][kBPaths];
+      simulate(chunk, x);
+#pragma unroll
+      for (int i = 0; i < A; ++i) {
+        float p = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kBPaths; ++j) p += j < nvalid ? x[i][j] : 0.0f;
+        acc[i] += static_cast<double>(p);
+      }
+      if constexpr (MODE == kBPriceRaw) payoffs(x, nvalid, sc);
+      if constexpr (MODE == kBPriceLds) {
+        // slot (chunk + 4 tid) / 4 of row i: chunk + 4 tid < P, so the slot ends at or before P4
+#pragma unroll
+        for (int i = 0; i < A; ++i)
+          park[(i * P4 + chunk) / kBPaths + tid] = v4f{x[i][0], x[i][1], x[i][2], x[i][3]};
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double w = bwave_sum(acc[i]);
+    if (lane == 0) wsum[wave * A + i] = w;
+  }
+  __syncthreads();
+  if (tid < A) {
+    double sum = 0.0;
+    for (int w = 0; w < kBWaves; ++w) sum += wsum[w * A + tid];
+    tot[tid] = sum;
+    if (a.terminal_sum) a.terminal_sum[b * A + tid] = sum;
+  }
+  if constexpr (MODE != kBPriceRaw) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < A; ++i) sc[i] = forward(i) / static_cast<float>(tot[i] / static_cast<double>(P));
+    // pass 2: the payoffs of the lane's own values, parked or simulated again
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float x[A][kBPaths];
+        if constexpr (MODE == kBPriceLds) {
+#pragma unroll
+          for (int i = 0; i < A; ++i) {
+            const v4f q = park[(i * P4 + chunk) / kBPaths + tid];
+#pragma unroll
+            for (int j = 0; j < kBPaths; ++j) x[i][j] = q[j];
+          }
+        } else {
+          simulate(chunk, x);
+        }
+        payoffs(x, nvalid, sc);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kBPriceSums; ++i) {
+    const double w = bwave_sum(v[i]);
+    if (lane == 0) lds[wave * kBPriceSums + i] = w;
+  }
+  __syncthreads();
+  auto total = [&](int i) {
+    double t = 0.0;
+    for (int w = 0; w < kBWaves; ++w) t += lds[w * kBPriceSums + i];
+    return t;
+  };
+  const double n = static_cast<double>(P);
+  double* out = prices + b * SMC_BASKET_PRICE_COLS;
+  if (tid < 6) {  // a payoff's mean and standard error
+    const double m = total(tid) / n;
+    double se = 0.0;
+    if (P > 1) {
+      const double var = total(6 + tid) - n * m * m;
+      se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+    }
+    out[tid] = m;
+    out[6 + tid] = se;
+  } else if (tid >= 12 && tid < kBPriceSums) {  // means of bk, mx, mn; the exercise share
+    out[tid] = total(tid) / n;
+  } else if (tid == kBPriceSums) {  // intrinsic basket put / call
+    float fs = 0.0f;
+#pragma unroll
+    for (int i = 0; i < A; ++i) fs = fs + forward(i);
+    const float ip = Kf - fs * wA, ic = fs * wA - Kf;
+    out[16] = static_cast<double>(df * (ip > 0.0f ? ip : 0.0f));
+    out[17] = static_cast<double>(df * (ic > 0.0f ? ic : 0.0f));
+  }
 }
 
 
@@ -809,6 +1057,51 @@ int32_t launch_basket(int A, const BasketArgs& a, hipStream_t stream) {
   }
 }
 
+// basket_price_kernel's mode and dynamic LDS for a shape (host only, no HIP call); -1: not a call it takes.
+// math: 0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY.
+int basket_price_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
+  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
+  *lds = kBPriceScratch;
+  if (normalization == SMC_NORM_RAW) return kBPriceRaw;
+  if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
+  const size_t park = kBPriceScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
+  if (park > kBPriceParkBytes) return kBPriceReplay;
+  *lds = park;
+  return kBPriceLds;
+}
+
+template <int A, bool HW>
+int32_t launch_basket_price_k(const BasketArgs& a, int mode, size_t lds, double* prices, hipStream_t stream) {
+  auto kernel = mode == kBPriceRaw   ? basket_price_kernel<A, HW, kBPriceRaw>
+                : mode == kBPriceLds ? basket_price_kernel<A, HW, kBPriceLds>
+                                     : basket_price_kernel<A, HW, kBPriceReplay>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "basket_price_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, prices);
+  return check_launch("basket_price_kernel");
+}
+
+template <bool HW>
+int32_t launch_basket_price(int A, const BasketArgs& a, int mode, size_t lds, double* prices, hipStream_t stream) {
+  switch (A) {
+    case 1: return launch_basket_price_k<1, HW>(a, mode, lds, prices, stream);
+    case 2: return launch_basket_price_k<2, HW>(a, mode, lds, prices, stream);
+    case 3: return launch_basket_price_k<3, HW>(a, mode, lds, prices, stream);
+    case 4: return launch_basket_price_k<4, HW>(a, mode, lds, prices, stream);
+    case 5: return launch_basket_price_k<5, HW>(a, mode, lds, prices, stream);
+    case 6: return launch_basket_price_k<6, HW>(a, mode, lds, prices, stream);
+    case 7: return launch_basket_price_k<7, HW>(a, mode, lds, prices, stream);
+    case 8: return launch_basket_price_k<8, HW>(a, mode, lds, prices, stream);
+    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: n_assets must be in 1..8");
+  }
+}
+
 }  // namespace
 }  // namespace smc
 
@@ -901,6 +1194,49 @@ const char* smc_basket_train_targets_kernel(int32_t n_assets, int32_t timesteps,
 int64_t smc_basket_resident_slots(int32_t n_assets, int32_t network_size, int32_t math) {
   if (n_assets < 1 || n_assets > kMaxAssets || network_size <= 0 || network_size > 4096) return -1;
   return math == SMC_MATH_HW ? basket_slots<true>(n_assets, network_size) : basket_slots<false>(n_assets, network_size);
+}
+
+int32_t smc_basket_price(const double* contracts_dev, int64_t n_contracts, int32_t n_assets, int32_t timesteps,
+                         int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
+                         int32_t normalization, double* prices_dev, double* terminal_sum_dev, void* stream) {
+  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: contracts_dev is NULL");
+  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: prices_dev is NULL");
+  if (n_assets < 1 || n_assets > kMaxAssets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: n_assets must be in 1..8");
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: bad normalization");
+  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
+  if (n_paths >= (int64_t{1} << 40)) return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price: n_paths too large (>= 2^40)");
+  if (n_contracts == 0) return SMC_OK;
+  size_t lds = 0;
+  const int mode = basket_price_mode(n_assets, n_paths, math, normalization, &lds);
+  BasketArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.normalize = normalization != SMC_NORM_RAW;
+  a.terminal_sum = terminal_sum_dev;
+  return (math & SMC_MATH_HW) ? launch_basket_price<true>(n_assets, a, mode, lds, prices_dev, as_stream(stream))
+                              : launch_basket_price<false>(n_assets, a, mode, lds, prices_dev, as_stream(stream));
+}
+
+const char* smc_basket_price_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                    int32_t normalization) {
+  size_t lds = 0;
+  if (timesteps <= 0) return "unsupported";
+  switch (basket_price_mode(n_assets, n_paths, math, normalization, &lds)) {
+    case kBPriceRaw: return "basket_price_kernel(raw)";
+    case kBPriceLds: return "basket_price_kernel(lds)";
+    case kBPriceReplay: return "basket_price_kernel(replay)";
+    default: return "unsupported";
+  }
 }
 
 #pragma GCC visibility pop
