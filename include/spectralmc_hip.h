@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 18  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price */
+#define SMC_ABI_VERSION 19  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -468,6 +468,64 @@ int32_t smc_basket_price(const double* contracts_dev /*[B][3A+4]*/, int64_t n_co
  * call smc_basket_price rejects).  Static string, no device call. */
 const char* smc_basket_price_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
                                     int32_t normalization);
+
+/* ---- batched Greeks (ABI 19) ----------------------------------------------------
+ * Pathwise sensitivities of the European put and call smc_gbm_price averages, for B contracts in ONE launch:
+ * the price call's workgroup per contract, streams (contract b uses ordinal (*ordinal_dev or 0) + ordinal0 + b),
+ * geometry, modes and fixed sum order, so the block is bit-identical run to run, under any split of the batch
+ * and in every mode.  SMC_SCHEME_LOG_EULER only: its terminal value x alone gives the path's log return
+ * L = log(x / X0) = mu T + v sqrt(dt) sum z and with it every derivative below; SMC_SCHEME_SIMPLE_EULER is
+ * rejected (SMC_ERR_INVALID_ARGUMENT), because its reflected step |x (1 + a + b z)| is not a function of the
+ * terminal value.  The estimators are the derivatives of the estimator smc_gbm_price computes, including,
+ * under SMC_NORM_NORMALIZE, the dependence of the scale F / mean(x) on the parameter.
+ * Per contract, each constant in f64 from the row X0 K T r d v, then rounded to the sim dtype Real:
+ *   F, df, K     as the price call's (F = X0 exp((r - d) T), df = exp(-r T), evaluated in Real)
+ *   s            F / Real(sumx / P) under NORMALIZE, 1 under RAW      mu = r - d - v^2 / 2
+ *   ix0 = Real(1 / X0)    cv = Real(1 / v), 0 if v == 0    cT = Real(1 / (2 T)), 0 if T == 0
+ *   crho = df * (Real(T) * K)    rr = Real(r)
+ *   RAW:        av = Real(-mu T / v - v T), 0 if v == 0         aT = Real(mu / 2)
+ *   NORMALIZE:  Lbar = sumxl / sumx (f64)   av = Real(-Lbar / v), 0 if v == 0
+ *               aT = Real(-Lbar / (2 T) + (r - d)), Real(r - d) if T == 0
+ *   sumx  = the f64 sum of the raw terminal values (the price call's column 7, bit for bit)
+ *   sumxl = sum over the paths of f64(x * L) (NORMALIZE only), L = log(x / Real(X0)) in Real: the portable f32
+ *           log, v_log_f32 times ln 2 under SMC_MATH_HW, the library log in f64.
+ * Per path, all in Real, every operation rounded (no fused multiply-add), each value cast to f64 and
+ * averaged over the P paths:
+ *   xs = x * s     ip = K - xs > 0     ic = xs - K > 0
+ *   put = df * max(K - xs, 0)    call = df * max(xs - K, 0)    w = df * xs
+ *   hv = L * cv + av  (d ln xs / d v)       hT = L * cT + aT  (d ln xs / d T)
+ *   delta  put: ip ? -(w * ix0) : 0         call: ic ? w * ix0 : 0
+ *   vega   put: ip ? -(w * hv) : 0          call: ic ? w * hv : 0
+ *   rho    put: ip ? -crho : 0              call: ic ? crho : 0
+ *   theta  put: rr * put + (ip ? w * hT : 0)   call: rr * call - (ic ? w * hT : 0)    (= -dV/dT, per year)
+ * gamma is not an estimator of its own: gamma = vega / (v T X0^2) in f64 (the lognormal identity, exact for the
+ * log-Euler terminal law), its standard error likewise; both 0 when v T == 0.
+ * greeks_dev [B][26]:
+ *    0 /  1 delta put / call       2 /  3 vega put / call       4 /  5 rho put / call
+ *    6 /  7 theta put / call       8 /  9 gamma put / call
+ *   10..19 the standard errors of columns 0..9 (the price call's formula; 0 at P = 1)
+ *   20 / 21 put / call price, 22 / 23 their standard errors: the price call's columns 0, 1, 3, 4 bit for bit
+ *   24 sumx: the price call's column 7 bit for bit         25 sumxl (0 under RAW).
+ * Conventions: v == 0 gives vega = gamma = 0 (and errors 0); T == 0 drops theta's hT * (1 / (2 T)) term and gives
+ * gamma = 0; P == 1 gives every standard error 0.  The standard errors take the P terms as independent: under
+ * NORMALIZE they leave out the sampling error of the shared s and Lbar.  NORMALIZE needs the terminal values twice: parked in LDS
+ * while the price call would park them (up to 144 KiB), else simulated a second time; SMC_PRICE_REPLAY forces
+ * the latter.  scheme takes SMC_MATH_HW (f32 only) and SMC_PRICE_REPLAY; SMC_MATH_REF and any other bit are
+ * rejected.  Checks, in this order and all before the empty batch (n_contracts = 0: SMC_OK, nothing touched)
+ * is accepted: the price call's (NULL contracts_dev, shape, dtype; NULL greeks_dev; bad scheme or unknown
+ * flag; SMC_MATH_REF; SMC_MATH_HW with f64; bad normalization), then the simple-Euler rejection.
+ * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  Contract values are not
+ * validated on the device, as elsewhere: X0 <= 0 gives NaN.  B below the CU count leaves CUs idle.
+ * Out of scope: simple Euler; Greeks of the path-dependent and basket payoffs; likelihood-ratio or
+ * second-order pathwise gamma; cross-Greeks. */
+#define SMC_GREEKS_COLS 26
+int32_t smc_gbm_greeks(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
+                       uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
+                       int32_t normalization, int32_t dtype, double* greeks_dev /*[B][26]*/, void* stream);
+/* "greeks_kernel(raw)", "greeks_kernel(lds)", "greeks_kernel(replay)" or "unsupported" (a call smc_gbm_greeks
+ * rejects, simple Euler among them).  Static string, no device call. */
+const char* smc_gbm_greeks_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                  int32_t dtype);
 
 #ifdef __cplusplus
 }

@@ -44,7 +44,8 @@ PRICE_REPLAY = 0x800  # smc_gbm_price scheme flag: never park the terminal value
 PRICE_COLS = 8  # doubles per contract smc_gbm_price writes
 PATH_PRICE_COLS = 20  # doubles per contract smc_gbm_price_paths writes
 BASKET_PRICE_COLS = 18  # doubles per contract smc_basket_price writes
-ABI_VERSION = 18
+GREEKS_COLS = 26  # doubles per contract smc_gbm_greeks writes
+ABI_VERSION = 19
 
 _c_i32, _c_i64, _c_u64, _c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
 
@@ -84,6 +85,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_gbm_price_paths": (_c_i32, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32,
                                      _c_i32, _c_vp, _c_vp]),
     "smc_gbm_price_paths_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
+    "smc_gbm_greeks": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32,
+                                _c_vp, _c_vp]),
+    "smc_gbm_greeks_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
     "smc_cvnn_plan": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_c_i64)]),
     "smc_cvnn_forward_backward": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64,
                                            _c_vp, _c_i64, _c_vp]),

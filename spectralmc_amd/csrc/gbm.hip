@@ -2057,6 +2057,222 @@ __global__ __launch_bounds__(kThreads) void path_price_kernel(EngineArgs a, cons
   }
 }
 
+// ---- batched Greeks: greeks_kernel (smc_gbm_greeks) ---------------------------------------------
+// price_kernel's geometry, streams, chunk loop, validity handling, modes and sum order (restated, not shared:
+// price_kernel's registers stay as they are), log-Euler only: the terminal value x_T alone gives the log return
+// L = log(x_T / X0) = mu T + v sqrt(dt) sum z, and with it every pathwise derivative of the payoffs price_kernel
+// averages (the table of include/spectralmc_hip.h), so the step loop is lane_rows_s as it
+// stands.  Per path ten values in Real (delta, vega, rho, theta, price; put and call), each cast to f64 and
+// added with its square: kGreekSums f64 sums per lane.  The pass-1 sums go through price_kernel's
+// [kWaves][kPriceSums] scratch and the parked row follows it, so the park bound is price_mode's; the final
+// [kWaves][kGreekSums] block lies over both once the row is no longer read (greeks_mode keeps the dynamic LDS
+// at least that large).  NORMALIZE takes a second sum in pass 1, sum f64(x L): the scale s = F / mean(x) moves
+// with the parameters, and its share of the derivatives is the x-weighted mean Lbar of L.  Only x is parked:
+// the payoff pass takes L from the same bits again.
+constexpr int kGreekTerms = 10;               // delta, vega, rho, theta, price: put and call
+constexpr int kGreekSums = 2 * kGreekTerms;   // the terms and their squares
+constexpr size_t kGreekScratch = kWaves * kGreekSums * sizeof(double);
+
+template <typename Real, bool HW>
+__device__ __forceinline__ Real greeks_log(Real x, Real x0) {
+  const Real q = x / x0;
+  if constexpr (sizeof(Real) == 8) return log(q);
+  else if constexpr (HW) return __builtin_amdgcn_logf(q) * 0.693147182f;
+  else return math::log_pos(q);
+}
+
+// The contract's constants of the pathwise weights: each from the f64 row (and, under NORMALIZE, the two
+// pass-1 sums) in f64, then rounded to Real.  v == 0 and T == 0 switch their terms off instead of dividing.
+template <typename Real>
+struct GreekConsts {
+  Real x0, ix0, cv, cT, crho, rr, av, aT;
+  __device__ GreekConsts(const Contract& c, const Payoff<Real>& pay, bool normalize, double sumx, double sumxl) {
+    const double mu = c.r - c.d - 0.5 * c.v * c.v;
+    x0 = static_cast<Real>(c.X0);
+    ix0 = static_cast<Real>(1.0 / c.X0);
+    cv = c.v == 0.0 ? Real(0) : static_cast<Real>(1.0 / c.v);
+    cT = c.T == 0.0 ? Real(0) : static_cast<Real>(1.0 / (2.0 * c.T));
+    crho = pay.df * (static_cast<Real>(c.T) * pay.K);
+    rr = static_cast<Real>(c.r);
+    if (normalize) {
+      const double lbar = sumxl / sumx;
+      av = c.v == 0.0 ? Real(0) : static_cast<Real>(-lbar / c.v);
+      aT = c.T == 0.0 ? static_cast<Real>(c.r - c.d) : static_cast<Real>(-lbar / (2.0 * c.T) + (c.r - c.d));
+    } else {
+      av = c.v == 0.0 ? Real(0) : static_cast<Real>(-mu * c.T / c.v - c.v * c.T);
+      aT = static_cast<Real>(mu / 2.0);
+    }
+  }
+};
+
+// One path's ten terms in Real (every operation rounded: contraction is off in this file), each cast to f64 and
+// added, its square added in f64.  put and call are price_add's.
+template <typename Real, bool HW>
+__device__ __forceinline__ void greeks_add(const Payoff<Real>& pay, const GreekConsts<Real>& g, Real x,
+                                           double (&v)[kGreekSums]) {
+  const Real L = greeks_log<Real, HW>(x, g.x0);
+  const Real xs = x * pay.s;
+  const Real dp = pay.K - xs, dc = xs - pay.K;
+  const bool ip = dp > Real(0), ic = dc > Real(0);
+  const Real put = pay.df * (ip ? dp : Real(0));
+  const Real call = pay.df * (ic ? dc : Real(0));
+  const Real w = pay.df * xs;
+  const Real hv = L * g.cv + g.av;
+  const Real hT = L * g.cT + g.aT;
+  const Real wd = w * g.ix0, wv = w * hv, wt = w * hT;
+  const Real t[kGreekTerms] = {ip ? -wd : Real(0),     ic ? wd : Real(0),
+                               ip ? -wv : Real(0),     ic ? wv : Real(0),
+                               ip ? -g.crho : Real(0), ic ? g.crho : Real(0),
+                               g.rr * put + (ip ? wt : Real(0)), g.rr * call - (ic ? wt : Real(0)),
+                               put, call};
+#pragma unroll
+  for (int i = 0; i < kGreekTerms; ++i) {
+    const double d = static_cast<double>(t[i]);
+    v[i] += d;
+    v[kGreekTerms + i] += d * d;
+  }
+}
+
+template <typename Real, bool HW, int MODE>
+__global__ __launch_bounds__(kThreads) void greeks_kernel(EngineArgs a, double* __restrict__ greeks) {
+  // [kWaves][kPriceSums] scratch, then (kPriceLds) the parked terminal row; at the end [kWaves][kGreekSums] over both
+  extern __shared__ double lds[];
+  if constexpr (sizeof(Real) == 8) math::f64_tables_load();
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  const double* const row = a.contracts + b * 6;
+  const Contract c = load_contract(row);
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+  const Stepper<Real, true, HW> step(c, T);
+  const Real x0 = static_cast<Real>(c.X0);
+  Real* park = reinterpret_cast<Real*>(lds + kWaves * kPriceSums);
+
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t p0 = chunk + kPathsPerLane * static_cast<int64_t>(tid);
+    return static_cast<int>(p0 >= P ? 0 : (P - p0 >= kPathsPerLane ? kPathsPerLane : P - p0));
+  };
+  // the lane's 4 terminal values of one chunk (nvalid > 0)
+  auto simulate = [&](int64_t chunk, Real (&xt)[kPathsPerLane]) {
+    const int64_t p0 = chunk + kPathsPerLane * static_cast<int64_t>(tid);
+    PathStream s(a.seed, ordinal, static_cast<uint64_t>(p0 / kPathsPerLane), T);
+    double unused = 0.0;
+    lane_rows_s<Real, true, HW, false, false>(s, step, x0, chunk, nullptr, T, 0, unused, xt, tid);
+  };
+
+  double v[kGreekSums];
+#pragma unroll
+  for (int i = 0; i < kGreekSums; ++i) v[i] = 0.0;
+  double sum[2] = {0.0, 0.0};  // x, and (NORMALIZE) x L
+
+  if constexpr (MODE == kPriceRaw) {
+    const Payoff<Real> pay(a, PayoffPre<Real>(c), 1.0);  // a.normalize == 0: scale 1
+    const GreekConsts<Real> g(c, pay, false, 0.0, 0.0);
+    for (int64_t chunk = 0; chunk < P; chunk += kChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        Real xt[kPathsPerLane];
+        simulate(chunk, xt);
+        Real part = 0;
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j) part += j < nvalid ? xt[j] : Real(0);
+        sum[0] += static_cast<double>(part);
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j)
+          if (j < nvalid) greeks_add<Real, HW>(pay, g, xt[j], v);
+      }
+    }
+    price_reduce(sum, lds);
+  } else {
+    for (int64_t chunk = 0; chunk < P; chunk += kChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        Real xt[kPathsPerLane];
+        simulate(chunk, xt);
+        Real part = 0;
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j) part += j < nvalid ? xt[j] : Real(0);
+        sum[0] += static_cast<double>(part);
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j) {
+          if (j < nvalid) {
+            sum[1] += static_cast<double>(xt[j] * greeks_log<Real, HW>(xt[j], x0));
+            if constexpr (MODE == kPriceLds) park[chunk + kPathsPerLane * tid + j] = xt[j];  // index < P
+          }
+        }
+      }
+    }
+    price_reduce(sum, lds);
+    // the contract row is read again: its six doubles are not held across the path loops
+    const Contract cr = load_contract(row);
+    const Payoff<Real> pay(a, PayoffPre<Real>(cr), sum[0]);
+    const GreekConsts<Real> g(cr, pay, true, sum[0], sum[1]);
+    for (int64_t chunk = 0; chunk < P; chunk += kChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        Real xt[kPathsPerLane];
+        if constexpr (MODE == kPriceLds) {  // the lane's own values: no barrier needed
+#pragma unroll
+          for (int j = 0; j < kPathsPerLane; ++j) xt[j] = j < nvalid ? park[chunk + kPathsPerLane * tid + j] : Real(0);
+        } else {
+          simulate(chunk, xt);
+        }
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j)
+          if (j < nvalid) greeks_add<Real, HW>(pay, g, xt[j], v);
+      }
+    }
+  }
+  // price_reduce's order (wave butterfly, then waves 0..7) with sum i totalled by thread i alone, as in
+  // path_price_kernel.  The [kWaves][kGreekSums] block lies over the scratch and the start of the parked row,
+  // which every lane has finished reading at the barrier (the host sizes the dynamic LDS for it).
+  __syncthreads();
+  {
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < kGreekSums; ++i) {
+      const double w = wave_sum(v[i]);
+      if (lane == 0) lds[wave * kGreekSums + i] = w;
+    }
+  }
+  __syncthreads();
+  if (tid < kGreekTerms) {  // term tid: its mean and standard error
+    auto total = [&](int i) {
+      double tot = 0.0;
+      for (int w = 0; w < kWaves; ++w) tot += lds[w * kGreekSums + i];
+      return tot;
+    };
+    const double n = static_cast<double>(P);
+    const double m = total(tid) / n;
+    double se = 0.0;
+    if (P > 1) {
+      const double var = total(kGreekTerms + tid) - n * m * m;
+      se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+    }
+    double* out = greeks + b * SMC_GREEKS_COLS;
+    if (tid < 8) {
+      out[tid] = m;
+      out[10 + tid] = se;
+    } else {  // the prices: columns 20, 21 and 22, 23
+      out[12 + tid] = m;
+      out[14 + tid] = se;
+    }
+    if (tid == 2 || tid == 3) {
+      // gamma from the lognormal identity vega = v T X0^2 gamma (exact for the log-Euler terminal law)
+      const Contract cr = load_contract(row);
+      const double vt = cr.v * cr.T;
+      const double den = vt * cr.X0 * cr.X0;
+      out[6 + tid] = vt == 0.0 ? 0.0 : m / den;
+      out[16 + tid] = vt == 0.0 ? 0.0 : se / den;
+    }
+    if (tid == 0) {
+      out[24] = sum[0];
+      out[25] = MODE == kPriceRaw ? 0.0 : sum[1];
+    }
+  }
+}
+
 template <typename Real, bool HW>
 __global__ __launch_bounds__(256) void normals_kernel(uint64_t seed, uint64_t ordinal, int32_t rows,
                                                       int64_t cols, Real* __restrict__ out) {
@@ -2559,6 +2775,38 @@ int32_t launch_path_price(const EngineArgs& a, const double* barriers, size_t ld
                    : launch_path_price_k<Real, false, false>(a, barriers, lds, rows, prices, stream);
 }
 
+// greeks_kernel's mode and dynamic LDS for a shape (host only, no HIP call): price_kernel's (the same scratch
+// and parked row) but never less than the final reduction block, log-Euler only; -1: not a shape it takes
+int greeks_mode(int64_t P, int32_t scheme, int32_t normalization, int32_t dtype, size_t* lds) {
+  if ((scheme & 0xff) != SMC_SCHEME_LOG_EULER) return -1;
+  const int mode = price_mode(P, scheme, normalization, dtype, lds);
+  if (mode >= 0 && *lds < kGreekScratch) *lds = kGreekScratch;  // the final reduction block, 1280 B
+  return mode;
+}
+
+template <typename Real, bool HW>
+int32_t launch_greeks_k(const EngineArgs& a, int mode, size_t lds, double* greeks, hipStream_t stream) {
+  auto kernel = mode == kPriceRaw   ? greeks_kernel<Real, HW, kPriceRaw>
+                : mode == kPriceLds ? greeks_kernel<Real, HW, kPriceLds>
+                                    : greeks_kernel<Real, HW, kPriceReplay>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "greeks_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kThreads), static_cast<uint32_t>(lds), stream, a, greeks);
+  return check_launch("greeks_kernel");
+}
+
+template <typename Real>
+int32_t launch_greeks(const EngineArgs& a, int mode, size_t lds, double* greeks, hipStream_t stream) {
+  if constexpr (sizeof(Real) == 4) {
+    if (a.scheme & SMC_MATH_HW) return launch_greeks_k<Real, true>(a, mode, lds, greeks, stream);
+  }
+  return launch_greeks_k<Real, false>(a, mode, lds, greeks, stream);
+}
+
 __global__ void advance_cursor_kernel(int64_t* cursor, int64_t advance) {
   if (threadIdx.x == 0) {
     cursor[0] += advance;
@@ -2989,6 +3237,53 @@ const char* smc_gbm_price_paths_kernel(int32_t timesteps, int64_t n_paths, int32
   switch (path_price_plan(timesteps, scheme, normalization, dtype, &lds, &rows)) {
     case 0: return "path_price_kernel(raw)";
     case 1: return "path_price_kernel(replay)";
+    default: return "unsupported";
+  }
+}
+
+int32_t smc_gbm_greeks(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
+                       uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
+                       int32_t normalization, int32_t dtype, double* greeks_dev, void* stream) {
+  if (int32_t st = validate_common(contracts_dev, n_contracts, timesteps, n_paths, dtype)) return st;
+  if (!greeks_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks: greeks_dev is NULL");
+  if (!valid_scheme(scheme & ~SMC_PRICE_REPLAY)) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks: bad scheme");
+  if (scheme & SMC_MATH_REF)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks: SMC_MATH_REF is for smc_train_targets / smc_train_step");
+  if ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks: SMC_MATH_HW is f32 only");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks: bad normalization");
+  if ((scheme & 0xff) != SMC_SCHEME_LOG_EULER)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_gbm_greeks: SMC_SCHEME_SIMPLE_EULER is not supported (the reflected step is not a function of "
+                "the terminal value); use SMC_SCHEME_LOG_EULER");
+  if (n_contracts == 0) return SMC_OK;
+  size_t lds = 0;
+  const int mode = greeks_mode(n_paths, scheme, normalization, dtype, &lds);
+  EngineArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.scheme = scheme & ~SMC_PRICE_REPLAY;
+  a.normalize = normalization != SMC_NORM_RAW;
+  return dtype == SMC_DTYPE_F32 ? launch_greeks<float>(a, mode, lds, greeks_dev, as_stream(stream))
+                                : launch_greeks<double>(a, mode, lds, greeks_dev, as_stream(stream));
+}
+
+const char* smc_gbm_greeks_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                  int32_t dtype) {
+  size_t lds = 0;
+  if (timesteps <= 0 || n_paths <= 0 || n_paths >= (1LL << 40) || !valid_scheme(scheme & ~SMC_PRICE_REPLAY) ||
+      (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE))
+    return "unsupported";
+  switch (greeks_mode(n_paths, scheme, normalization, dtype, &lds)) {
+    case kPriceRaw: return "greeks_kernel(raw)";
+    case kPriceLds: return "greeks_kernel(lds)";
+    case kPriceReplay: return "greeks_kernel(replay)";
     default: return "unsupported";
   }
 }

@@ -6,7 +6,8 @@ Public names and semantics follow the reference: ``SimulationParams`` /
 ``price_batch`` / ``price_batch_device`` (not in the reference) price many contracts in one
 launch of the fused pricing kernel (``smc_gbm_price``); ``price_paths_batch`` /
 ``price_paths_batch_device`` do the same for the path-dependent payoffs (average-price, knock-out,
-fixed-strike lookback) monitored at the time grid (``smc_gbm_price_paths``).
+fixed-strike lookback) monitored at the time grid (``smc_gbm_price_paths``); ``greeks_batch`` /
+``greeks_batch_device`` give the pathwise Greeks of the European pair on the same paths (``smc_gbm_greeks``).
 
 What changed underneath:
 * the normal matrix of contract m is not materialised: ``smc_gbm_simulate`` draws it in
@@ -236,6 +237,71 @@ class BlackScholes:
         mean_min: float
         knock_in_put: float
         knock_in_call: float
+
+        model_config = ConfigDict(frozen=True, extra="forbid")
+
+    class BatchGreeks(BaseModel):
+        """``smc_gbm_greeks``' block for B contracts, column by column: ``[B]`` f64 device tensors (pathwise
+        delta, vega, rho, theta = -dV/dT per year, gamma from the lognormal identity; their standard errors; the
+        prices ``price_batch_device`` gives on the same paths; the two terminal sums)."""
+
+        model_config = ConfigDict(arbitrary_types_allowed=True, extra="forbid")
+        put_delta: torch.Tensor
+        call_delta: torch.Tensor
+        put_vega: torch.Tensor
+        call_vega: torch.Tensor
+        put_rho: torch.Tensor
+        call_rho: torch.Tensor
+        put_theta: torch.Tensor
+        call_theta: torch.Tensor
+        put_gamma: torch.Tensor
+        call_gamma: torch.Tensor
+        put_delta_stderr: torch.Tensor
+        call_delta_stderr: torch.Tensor
+        put_vega_stderr: torch.Tensor
+        call_vega_stderr: torch.Tensor
+        put_rho_stderr: torch.Tensor
+        call_rho_stderr: torch.Tensor
+        put_theta_stderr: torch.Tensor
+        call_theta_stderr: torch.Tensor
+        put_gamma_stderr: torch.Tensor
+        call_gamma_stderr: torch.Tensor
+        put_price: torch.Tensor
+        call_price: torch.Tensor
+        put_stderr: torch.Tensor
+        call_stderr: torch.Tensor
+        terminal_sum: torch.Tensor
+        terminal_log_sum: torch.Tensor
+
+    class HostGreeks(BaseModel):
+        """One contract's row of ``BatchGreeks`` on the host."""
+
+        put_delta: float
+        call_delta: float
+        put_vega: float
+        call_vega: float
+        put_rho: float
+        call_rho: float
+        put_theta: float
+        call_theta: float
+        put_gamma: float
+        call_gamma: float
+        put_delta_stderr: float
+        call_delta_stderr: float
+        put_vega_stderr: float
+        call_vega_stderr: float
+        put_rho_stderr: float
+        call_rho_stderr: float
+        put_theta_stderr: float
+        call_theta_stderr: float
+        put_gamma_stderr: float
+        call_gamma_stderr: float
+        put_price: float
+        call_price: float
+        put_stderr: float
+        call_stderr: float
+        terminal_sum: float
+        terminal_log_sum: float
 
         model_config = ConfigDict(frozen=True, extra="forbid")
 
@@ -475,6 +541,63 @@ class BlackScholes:
             out.append(self.HostPathPrices(knock_in_put=cols["put_price"] - cols["knock_out_put"],
                                            knock_in_call=cols["call_price"] - cols["knock_out_call"], **cols))
         return Success(out)
+
+    # ------------------------------------------------------------------ batched Greeks
+    def _greeks_block(self, contracts: torch.Tensor) -> Result[torch.Tensor, NormalsError]:
+        """One ``smc_gbm_greeks`` launch on the current stream (no sync): the ``[B, 26]`` f64 block of
+        contracts ``[B, 6]`` f64 on the device; contract b takes ordinal ``ordinal + b``."""
+        if self._cfg.path_scheme is not PathScheme.LOG_EULER:
+            raise ValueError(f"greeks_batch needs PathScheme.LOG_EULER, got {self._cfg.path_scheme.name}: the pathwise "
+                             "Greeks are functions of the log-Euler terminal value")
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if contracts.ndim != 2 or contracts.shape[1] != len(FIELDS) or contracts.dtype != torch.float64:
+            raise ValueError(f"contracts must be a [B, {len(FIELDS)}] float64 tensor, got "
+                             f"{tuple(contracts.shape)} {contracts.dtype}")
+        _lib.require_device()
+        if not contracts.is_cuda:
+            raise ValueError("contracts must be a device tensor")
+        sp = self._sp
+        contracts = contracts.contiguous()
+        B = int(contracts.shape[0])
+        block = torch.empty((B, _lib.GREEKS_COLS), dtype=torch.float64, device=contracts.device)
+        if self.price_batch_math not in ("portable", "hw"):
+            raise ValueError(f"price_batch_math must be 'portable' or 'hw', got {self.price_batch_math!r}")
+        scheme = scheme_code(self._cfg.path_scheme) | (_lib.MATH_HW if self.price_batch_math == "hw" else 0)
+        if B:
+            _lib.check(_lib.lib().smc_gbm_greeks(
+                _lib.ptr(contracts), B, sp.timesteps, sp.total_paths(), sp.mc_seed, None, self._served,
+                scheme, normalization_code(self._cfg.normalization), dtype_code(sp.dtype),
+                _lib.ptr(block), _lib.stream_handle()))
+            self._served += B
+        return Success(block)
+
+    def greeks_batch_device(self, contracts: torch.Tensor) -> Result["BlackScholes.BatchGreeks", NormalsError]:
+        """Pathwise Greeks of the European put and call of B contracts (``[B, 6]`` f64 device tensor, columns
+        X0 K T r d v) in one launch of the fused kernel, with no path matrix in memory and no host sync: the
+        derivatives of the estimator ``price_batch_device`` computes, on the same paths, with their standard
+        errors.  LOG_EULER engines only.  Consumes the normal streams of B ``price`` calls."""
+        res = self._greeks_block(contracts)
+        if isinstance(res, Failure):
+            return res
+        return Success(self.BatchGreeks(**dict(zip(self.BatchGreeks.model_fields, res.value.unbind(dim=1)))))
+
+    def greeks_batch(self, inputs: "Sequence[BlackScholes.Inputs]"
+                     ) -> Result["list[BlackScholes.HostGreeks]", NormalsError]:
+        """``greeks_batch_device`` from host values: one launch and one device-to-host copy."""
+        if self._cfg.path_scheme is not PathScheme.LOG_EULER:
+            raise ValueError(f"greeks_batch needs PathScheme.LOG_EULER, got {self._cfg.path_scheme.name}: the pathwise "
+                             "Greeks are functions of the log-Euler terminal value")
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if len(inputs) == 0:
+            return Success([])
+        rows = [[float(getattr(c, f)) for f in FIELDS] for c in inputs]
+        res = self._greeks_block(torch.tensor(rows, dtype=torch.float64, device=self._device()))
+        if isinstance(res, Failure):
+            return res
+        names = list(self.BatchGreeks.model_fields)
+        return Success([self.HostGreeks(**dict(zip(names, row))) for row in res.value.cpu().tolist()])
 
 
 def intrinsic_values(contract: "BlackScholes.Inputs") -> tuple[float, float, float]:
