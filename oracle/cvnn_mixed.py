@@ -11,6 +11,12 @@ operand precision of the MFMA kernels (spectralmc_amd/csrc/cvnn_mfma.hip) made e
   f32 on the matrix cores — the only difference the parity tests allow for;
 * bias, activation, loss, activation backward run in f32 (loss summed in f64), as the kernels do.
 
+``operand="f64"`` is the high-precision reference of the kernel tests (tests/test_gpu_cvnn_kernels.py):
+parameters and inputs are widened as given and every operation runs in float64, the ``1e-9`` under
+modReLU's modulus included.  ``accumulate="f32"`` sums the same (operand-rounded) products one after
+the other in f32 instead of exactly: the difference between the two is how sensitive a gradient is to
+the order of an f32 accumulation.  ``adam_reference`` restates ``adam_update`` of csrc/cvnn.hip.
+
 The bf16 mode is the build's extension for BASELINE.json configs[2] ("bf16 CVNN"); the reference
 asserts full precision (gbm_trainer.py:679-686), so its parity is against this restatement.
 
@@ -38,11 +44,13 @@ def _rounder(operand: str):
         return bf16_round
     if operand == "f32":
         return lambda x: np.asarray(x, dtype=np.float32)
+    if operand == "f64":
+        return lambda x: np.asarray(x, dtype=np.float64)
     raise ValueError(operand)
 
 
 def _interleave(re: np.ndarray, im: np.ndarray) -> np.ndarray:
-    out = np.empty((re.shape[0], 2 * re.shape[1]), dtype=np.float32)
+    out = np.empty((re.shape[0], 2 * re.shape[1]), dtype=re.dtype)
     out[:, 0::2] = re
     out[:, 1::2] = im
     return out
@@ -52,7 +60,7 @@ def _wc(params: np.ndarray, ni: int, no: int, w_re: int, w_im: int) -> np.ndarra
     """Real [2 no][2 ni] map of the complex weight A + iB: blocks [[A, -B], [B, A]]."""
     A = params[w_re:w_re + no * ni].reshape(no, ni)
     Bm = params[w_im:w_im + no * ni].reshape(no, ni)
-    W = np.empty((2 * no, 2 * ni), dtype=np.float32)
+    W = np.empty((2 * no, 2 * ni), dtype=params.dtype)
     W[0::2, 0::2] = A
     W[0::2, 1::2] = -Bm
     W[1::2, 0::2] = Bm
@@ -60,8 +68,22 @@ def _wc(params: np.ndarray, ni: int, no: int, w_re: int, w_im: int) -> np.ndarra
     return W
 
 
+def _mm(a: np.ndarray, b: np.ndarray, accumulate: str, f: type) -> np.ndarray:
+    """a @ b: the products summed exactly (float64) and rounded once to ``f``, or ("f32") added one after
+    the other in f32 (products of bf16 operands are exact in f32)."""
+    if accumulate == "exact":
+        return (a.astype(np.float64) @ b.astype(np.float64)).astype(f)
+    if accumulate != "f32":
+        raise ValueError(accumulate)
+    a32, b32 = a.astype(np.float32), b.astype(np.float32)
+    acc = np.zeros((a.shape[0], b.shape[1]), dtype=np.float32)
+    for k in range(a.shape[1]):
+        acc += a32[:, k, None] * b32[None, k, :]
+    return acc.astype(f)
+
+
 def _act_fwd(act: int, c: np.ndarray, u: np.ndarray, v: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-    f = np.float32
+    f = u.dtype.type
     if act == ACT_MODRELU:
         m = np.sqrt(u * u + v * v + f(1e-9))
         g = np.maximum(m + c, f(0)) / m
@@ -74,7 +96,7 @@ def _act_fwd(act: int, c: np.ndarray, u: np.ndarray, v: np.ndarray) -> tuple[np.
 
 def _act_bwd(act: int, c: np.ndarray, u: np.ndarray, v: np.ndarray, gr: np.ndarray,
              gi: np.ndarray) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-    f = np.float32
+    f = u.dtype.type
     if act == ACT_MODRELU:
         m = np.sqrt(u * u + v * v + f(1e-9))
         on = m + c > 0
@@ -90,20 +112,22 @@ def _act_bwd(act: int, c: np.ndarray, u: np.ndarray, v: np.ndarray, gr: np.ndarr
 
 
 def cvnn_step(layers, params: np.ndarray, x_re: np.ndarray, x_im: np.ndarray | None, targets: np.ndarray,
-              operand: str = "bf16") -> tuple[float, np.ndarray]:
-    """Loss and the flat f32 gradient of one network step (before Adam)."""
+              operand: str = "bf16", accumulate: str = "exact",
+              pre_out: list | None = None) -> tuple[float, np.ndarray]:
+    """Loss and the flat gradient (f32; float64 for ``operand="f64"``) of one network step (before Adam).
+    ``pre_out``, a list, receives each layer's (activation, u, v, c): its pre-activations and modReLU bias."""
     rnd = _rounder(operand)
-    f = np.float32
-    params = np.asarray(params, dtype=np.float32)
-    x_re = np.asarray(x_re, dtype=np.float32)
-    x_im = np.zeros_like(x_re) if x_im is None else np.asarray(x_im, dtype=np.float32)
+    f = np.float64 if operand == "f64" else np.float32
+    params = np.asarray(params, dtype=f)
+    x_re = np.asarray(x_re, dtype=f)
+    x_im = np.zeros_like(x_re) if x_im is None else np.asarray(x_im, dtype=f)
     B = x_re.shape[0]
     N = layers[-1][1]
     z = rnd(_interleave(x_re, x_im))
     zs, pres, wcs = [], [], []
     for (ni, no, act, w_re, w_im, b_re, b_im, act_bias) in layers:
         wc = rnd(_wc(params, ni, no, w_re, w_im))
-        pre = (z.astype(np.float64) @ wc.astype(np.float64).T).astype(f)
+        pre = _mm(z, wc.T, accumulate, f)
         u, v = pre[:, 0::2].copy(), pre[:, 1::2].copy()
         if b_re >= 0:
             u += params[b_re:b_re + no]
@@ -113,9 +137,11 @@ def cvnn_step(layers, params: np.ndarray, x_re: np.ndarray, x_im: np.ndarray | N
         ou, ov = _act_fwd(act, c, u, v)
         zs.append(z)
         pres.append((u, v, c))
+        if pre_out is not None:
+            pre_out.append((act, u, v, c))
         wcs.append(wc)
         z = rnd(_interleave(ou, ov))
-    t = np.asarray(targets).astype(np.complex64)
+    t = np.asarray(targets).astype(np.complex128 if operand == "f64" else np.complex64)
     dr, di = ou - t.real, ov - t.imag
     loss = float((dr.astype(np.float64) ** 2).sum() + (di.astype(np.float64) ** 2).sum()) / (B * N)
     scale = f(2.0 / (float(B) * N))
@@ -127,19 +153,42 @@ def cvnn_step(layers, params: np.ndarray, x_re: np.ndarray, x_im: np.ndarray | N
         gu, gv, dc = _act_bwd(act, c, u, v, gr, gi)
         if act == ACT_MODRELU:
             grads[act_bias:act_bias + no] = dc.astype(np.float64).sum(axis=0).astype(f)
-        gU = rnd(_interleave(gu, gv)).astype(np.float64)
-        dW = (gU.T @ zs[l].astype(np.float64)).astype(f)  # [2 no][2 ni]
+        gU = rnd(_interleave(gu, gv))
+        dW = _mm(gU.T, zs[l], accumulate, f)  # [2 no][2 ni]
         grads[w_re:w_re + no * ni] = (dW[0::2, 0::2] + dW[1::2, 1::2]).reshape(-1)
         grads[w_im:w_im + no * ni] = (dW[1::2, 0::2] - dW[0::2, 1::2]).reshape(-1)
-        db = gU.sum(axis=0).astype(f)
+        db = _mm(gU.T, np.ones((B, 1), dtype=f), accumulate, f)[:, 0]
         if b_re >= 0:
             grads[b_re:b_re + no] = db[0::2]
         if b_im >= 0:
             grads[b_im:b_im + no] = db[1::2]
         if l > 0:
-            gz = (gU @ wcs[l].astype(np.float64)).astype(f)
+            gz = _mm(gU, wcs[l], accumulate, f)
             gr, gi = gz[:, 0::2], gz[:, 1::2]
     return loss, grads
 
 
-__all__ = ["bf16_round", "cvnn_step"]
+def adam_reference(params, m, v, g, step, lr, b1, b2, eps, weight_decay, real=np.float64):
+    """``adam_update`` of csrc/cvnn.hip (torch's Adam with L2 weight decay) in float64 on float64 arrays.
+
+    The hyper-parameters are what the kernel computes with, ``real(lr)`` ... widened, and the two bias
+    corrections ``1 - b^t`` are taken in ``real`` (np.float32 or np.float64) from the f32 step counter, as
+    the kernel takes them from torch's capturable counter: in f32 their rounding is part of the operation,
+    not an error of it.  Returns (params, exp_avg, exp_avg_sq, gradient norm, step) after the update; the norm
+    is that of ``g`` as given, before the weight-decay term."""
+    p, m, v, g = (np.asarray(a, dtype=np.float64) for a in (params, m, v, g))
+    t = real(np.float32(step)) + real(1)
+    rb1, rb2 = real(b1), real(b2)
+    bc1 = float(real(1) - np.power(rb1, t))
+    bc2 = float(real(1) - np.power(rb2, t))
+    lr, b1, b2, eps, wd = float(real(lr)), float(rb1), float(rb2), float(real(eps)), float(real(weight_decay))
+    grad_norm = float(np.sqrt((g * g).sum()))
+    if weight_decay != 0.0:
+        g = g + wd * p
+    mm = m + (1.0 - b1) * (g - m)
+    vv = v * b2 + (1.0 - b2) * g * g
+    denom = np.sqrt(vv) / np.sqrt(bc2) + eps
+    return p - (lr / bc1) * (mm / denom), mm, vv, grad_norm, float(np.float32(step) + np.float32(1))
+
+
+__all__ = ["adam_reference", "bf16_round", "cvnn_step"]
