@@ -68,8 +68,8 @@ extern "C" {
                                       stored f32 value equals the reference arithmetic's except where the
                                       two exps round to different floats (C2 shape: <= 1e-6 of the values,
                                       1 ulp; tests/test_oracle.py).  With SMC_MATH_HW (ABI 15): the same
-                                      step on the hardware-transcendental f32 normals (~1 ulp from the
-                                      portable ones, so not bit-reproducible on a CPU).  In the kernel
+                                      step on the hardware-transcendental f32 normals (within 1.1e-6 of
+                                      the exact ones, so not bit-reproducible on a CPU).  In the kernel
                                       queries' dtype: that kernel's name */
 #define SMC_TRAIN_DYNAMIC    0x200  /* flag, OR into smc_train_step's `scheme`: the whole-contract resident
                                       launch hands out every contract from its contract queue (default:

@@ -130,8 +130,20 @@ static void sincos2pi_u24(uint32_t j, float* s_out, float* c_out) {
   *c_out = u2f(f2u(odd ? s : c) ^ cflip);
 }
 
+/* float -> int as the device converts it (v_cvt_i32_f32): saturating, NaN -> 0 (a bare C cast is undefined
+ * out of range) */
+static int f2i_sat(float n) {
+  if (n != n) return 0;
+  if (n >= 2147483648.0f) return INT32_MAX;
+  if (n <= -2147483648.0f) return INT32_MIN;
+  return (int)n;
+}
+
+/* Outside [-150, 128]: 0 below -150 for every finite y (the conversion of n saturates) and inf from 128 up, +inf
+ * included (n stops at 128, f = y - 128 >= 0, the polynomial is >= 1 or inf); NaN for NaN (fminf drops it, f keeps
+ * it) and for -inf (f = inf - inf). */
 static float exp2_any(float y) {
-  const float n = rintf(y);
+  const float n = rintf(fminf(y, 128.0f));
   const float f = y - n;
   float p = 0.00015337577497120947f;
   p = fmaf(p, f, 0.0013399859890341759f);
@@ -140,7 +152,7 @@ static float exp2_any(float y) {
   p = fmaf(p, f, 0.24022646248340607f);
   p = fmaf(p, f, 0.6931471824645996f);
   p = fmaf(p, f, 1.0f);
-  return ldexpf(p, (int)n);
+  return ldexpf(p, f2i_sat(n));
 }
 
 static float exp_any(float x) { return exp2_any(x * 1.44269502f); }
@@ -285,24 +297,82 @@ void oracle_stream_u32(uint64_t seed, uint64_t ordinal, uint64_t group, int64_t 
 
 /* One Box-Muller pair.  f32: 23-bit uniforms and the portable kernels (bit-identical to the
  * device); f64: 32-bit uniforms and the m2log_u32 / sincos2pi_u32 sequences above (bit-identical). */
+static void box_muller_f32(uint32_t a, uint32_t b, float* z0, float* z1) {
+  /* u1 = 2 - (1.m) with m = a >> 9: (0, 1] on the 2^-23 grid, exact; angle (b >> 9) 2^-23 rev */
+  const float u1 = 2.0f - u2f(0x3F800000u | (a >> 9));
+  const float r = sqrtf(-2.0f * log_pos(u1));
+  float sn, cs;
+  sincos2pi_u24((b >> 9) << 1, &sn, &cs);
+  *z0 = r * cs;
+  *z1 = r * sn;
+}
+
+static void box_muller_f64(uint32_t a, uint32_t b, double* z0, double* z1) {
+  /* u1 = (a + 1/2) 2^-32, the angle of b (sincos2pi_u32): smc_math.h m2log_u32 / sincos2pi_u32 */
+  const double r = sqrt(m2log_u32(a));
+  double sn, cs;
+  sincos2pi_u32(b, &sn, &cs);
+  *z0 = r * cs;
+  *z1 = r * sn;
+}
+
 static void normal_pair(mwc64x* g, int is_f64, double* z0, double* z1) {
   const uint32_t a = mwc_next(g), b = mwc_next(g);
   if (is_f64) {
-    /* u1 = (a + 1/2) 2^-32, the angle of b (sincos2pi_u32): smc_math.h m2log_u32 / sincos2pi_u32 */
-    const double r = sqrt(m2log_u32(a));
-    double sn, cs;
-    sincos2pi_u32(b, &sn, &cs);
-    *z0 = r * cs;
-    *z1 = r * sn;
+    box_muller_f64(a, b, z0, z1);
   } else {
-    /* u1 = 2 - (1.m) with m = a >> 9: (0, 1] on the 2^-23 grid, exact; angle (b >> 9) 2^-23 rev */
-    const float u1 = 2.0f - u2f(0x3F800000u | (a >> 9));
-    const float r = sqrtf(-2.0f * log_pos(u1));
-    float sn, cs;
-    sincos2pi_u24((b >> 9) << 1, &sn, &cs);
-    *z0 = (double)(r * cs);
-    *z1 = (double)(r * sn);
+    float f0, f1;
+    box_muller_f32(a, b, &f0, &f1);
+    *z0 = (double)f0;
+    *z1 = (double)f1;
   }
+}
+
+/* Array forms of the math above for exhaustive sweeps (tests/test_math_accuracy.py, tests/test_gpu_math.py): each a
+ * loop over the static functions; output pairs interleaved as smc_test_math_eval lays them out. */
+void oracle_log_pos_n(const float* u, int64_t n, float* out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) out[i] = log_pos(u[i]);
+}
+void oracle_sincos2pi_u24_n(const uint32_t* j, int64_t n, float* sc) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) sincos2pi_u24(j[i], &sc[2 * i], &sc[2 * i + 1]);
+}
+void oracle_exp2_n(const float* y, int64_t n, float* out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) out[i] = exp2_any(y[i]);
+}
+void oracle_exp_n(const float* x, int64_t n, float* out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) out[i] = exp_any(x[i]);
+}
+void oracle_normal_f32_n(const uint32_t* a, const uint32_t* b, int64_t n, float* z) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) box_muller_f32(a[i], b[i], &z[2 * i], &z[2 * i + 1]);
+}
+void oracle_m2log_u32_n(const uint32_t* a, int64_t n, double* out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) out[i] = m2log_u32(a[i]);
+}
+void oracle_sincos2pi_u32_n(const uint32_t* b, int64_t n, double* sc) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) sincos2pi_u32(b[i], &sc[2 * i], &sc[2 * i + 1]);
+}
+void oracle_exp2s_f64_n(const double* ys, int64_t n, double* out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) out[i] = oracle_exp2s_f64(ys[i]);
+}
+void oracle_mul_exp2s_f64_n(const double* x_ys, int64_t n, double* out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) out[i] = oracle_mul_exp2s_f64(x_ys[2 * i], x_ys[2 * i + 1]);
+}
+void oracle_normal_f64_n(const uint32_t* a, const uint32_t* b, int64_t n, double* z) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) box_muller_f64(a[i], b[i], &z[2 * i], &z[2 * i + 1]);
+}
+void oracle_twiddle_n(const int64_t* j_N, int64_t n, double* sc) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) twiddle(j_N[2 * i], j_N[2 * i + 1], &sc[2 * i], &sc[2 * i + 1]);
 }
 
 /* Normals of one group of 4 paths: z[t][j] for t < rows (f64 holder of dtype values).  Step pairs

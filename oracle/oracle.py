@@ -82,6 +82,11 @@ def lib() -> ctypes.CDLL:
         L.oracle_log_pos.restype = ctypes.c_float
         L.oracle_exp2.argtypes = [ctypes.c_float]
         L.oracle_exp2.restype = ctypes.c_float
+        for name in ("oracle_log_pos_n", "oracle_sincos2pi_u24_n", "oracle_exp2_n", "oracle_exp_n", "oracle_m2log_u32_n",
+                     "oracle_sincos2pi_u32_n", "oracle_exp2s_f64_n", "oracle_mul_exp2s_f64_n", "oracle_twiddle_n"):
+            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        for name in ("oracle_normal_f32_n", "oracle_normal_f64_n"):
+            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -127,6 +132,77 @@ def exp2s_f64(ys: float) -> float:
     """2^(ys / 256) as the f64 device path recursion computes it, the exponent in units of ln 2 / 256
     (csrc/smc_math.h exp2s_f64)."""
     return float(lib().oracle_exp2s_f64(ys))
+
+
+# Array forms of the math restatements (exhaustive sweeps: one C loop per call).  Pair outputs have a last axis of 2.
+def _map_n(name: str, x: np.ndarray, in_dtype: type, in_width: int, out_dtype: type, out_width: int) -> np.ndarray:
+    x = np.ascontiguousarray(x, dtype=in_dtype)
+    n = x.size // in_width
+    assert x.size == n * in_width
+    out = np.empty((n, out_width) if out_width > 1 else n, dtype=out_dtype)
+    getattr(lib(), name)(_ptr(x), n, _ptr(out))
+    return out
+
+
+def log_pos_n(u: np.ndarray) -> np.ndarray:
+    """ln u of positive normal f32 (csrc/smc_math.h log_pos)."""
+    return _map_n("oracle_log_pos_n", u, np.float32, 1, np.float32, 1)
+
+
+def sincos2pi_u24_n(j: np.ndarray) -> np.ndarray:
+    """[n, 2] (sin, cos)(2 pi j 2^-24), j < 2^24 (csrc/smc_math.h sincos2pi_u24)."""
+    return _map_n("oracle_sincos2pi_u24_n", j, np.uint32, 1, np.float32, 2)
+
+
+def exp2_n(y: np.ndarray) -> np.ndarray:
+    """2^y in f32 (csrc/smc_math.h exp2_any)."""
+    return _map_n("oracle_exp2_n", y, np.float32, 1, np.float32, 1)
+
+
+def exp_n(x: np.ndarray) -> np.ndarray:
+    """e^x in f32 (csrc/smc_math.h exp_any)."""
+    return _map_n("oracle_exp_n", x, np.float32, 1, np.float32, 1)
+
+
+def m2log_u32_n(a: np.ndarray) -> np.ndarray:
+    return _map_n("oracle_m2log_u32_n", a, np.uint32, 1, np.float64, 1)
+
+
+def sincos2pi_u32_n(b: np.ndarray) -> np.ndarray:
+    """[n, 2] (sin, cos) of the f64 Box-Muller angle of b."""
+    return _map_n("oracle_sincos2pi_u32_n", b, np.uint32, 1, np.float64, 2)
+
+
+def exp2s_f64_n(ys: np.ndarray) -> np.ndarray:
+    return _map_n("oracle_exp2s_f64_n", ys, np.float64, 1, np.float64, 1)
+
+
+def mul_exp2s_f64_n(x_ys: np.ndarray) -> np.ndarray:
+    """x 2^(ys / 256) of [n, 2] rows (x, ys) (csrc/smc_math.h mul_exp2s_f64)."""
+    return _map_n("oracle_mul_exp2s_f64_n", x_ys, np.float64, 2, np.float64, 1)
+
+
+def twiddle_n(j_N: np.ndarray) -> np.ndarray:
+    """[n, 2] (sin, cos)(2 pi j / N) of [n, 2] int64 rows (j, N) (csrc/smc_math.h twiddle)."""
+    return _map_n("oracle_twiddle_n", j_N, np.int64, 2, np.float64, 2)
+
+
+def _normal_n(name: str, a: np.ndarray, b: np.ndarray, out_dtype: type) -> np.ndarray:
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=np.uint32), np.asarray(b, dtype=np.uint32))
+    a, b = np.ascontiguousarray(a).ravel(), np.ascontiguousarray(b).ravel()
+    out = np.empty((a.size, 2), dtype=out_dtype)
+    getattr(lib(), name)(_ptr(a), _ptr(b), a.size, _ptr(out))
+    return out
+
+
+def normal_f32_n(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """[n, 2] (z0, z1): the portable f32 Box-Muller of the stream words (a, b) (csrc/smc_rng.h box_muller<false>)."""
+    return _normal_n("oracle_normal_f32_n", a, b, np.float32)
+
+
+def normal_f64_n(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """[n, 2] (z0, z1): the f64 Box-Muller of the stream words (a, b) (csrc/smc_rng.h box_muller, double)."""
+    return _normal_n("oracle_normal_f64_n", a, b, np.float64)
 
 
 def normals(seed: int, ordinal: int, rows: int, cols: int, dtype: str = "float32") -> np.ndarray:

@@ -112,7 +112,12 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
 # include/spectralmc_hip_testing.h: test-only entry points, inert unless SMC_ENABLE_TEST_HOOKS=1
 TEST_SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_test_exchange_fault": (_c_i32, [_c_i32, ctypes.c_uint32]),
+    "smc_test_math_eval": (_c_i32, [_c_i32, _c_vp, _c_i64, _c_vp, _c_vp]),
 }
+# smc_test_math_eval function ids (spectralmc_hip_testing.h SMC_TEST_MATH_*)
+TEST_MATH = {name: i for i, name in enumerate((
+    "LOG_POS", "SINCOS_U24", "EXP2_ANY", "EXP_ANY", "NORMAL_F32", "NORMAL_F32_HW", "HW_INCREMENT", "HW_EXP2", "HW_LOG",
+    "M2LOG_U32", "SQRT_RADIUS", "SINCOS_U32", "EXP2S", "MUL_EXP2S", "NORMAL_F64", "TWIDDLE"))}
 
 CVNN_MAX_LAYERS = 8
 ACT_NONE, ACT_MODRELU, ACT_ZRELU = 0, 1, 2

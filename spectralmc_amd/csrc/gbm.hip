@@ -2077,7 +2077,7 @@ template <typename Real, bool HW>
 __device__ __forceinline__ Real greeks_log(Real x, Real x0) {
   const Real q = x / x0;
   if constexpr (sizeof(Real) == 8) return log(q);
-  else if constexpr (HW) return __builtin_amdgcn_logf(q) * 0.693147182f;
+  else if constexpr (HW) return math::hw_log(q);
   else return math::log_pos(q);
 }
 

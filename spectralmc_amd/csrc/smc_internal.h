@@ -77,6 +77,10 @@ inline int stream_cus(hipStream_t stream, int cus) {
 // targets for the contracts it could not finish.
 constexpr uint32_t kExchangeSpinLimit = 1u << 20;
 
+// The switch of every entry point of spectralmc_hip_testing.h: SMC_ENABLE_TEST_HOOKS=1 in the environment at the
+// first call of any of them (capi.hip).
+bool test_hooks_enabled();
+
 // Test hook (smc_test_exchange_fault): applied by the host to the next exchanging launches.
 struct ExchangeFault {
   int32_t withhold;     // 1: slice W-1 of group 0 skips its first arrival

@@ -10,8 +10,13 @@
 // Cost on CDNA4: the hardware transcendentals issue at quarter rate, so these full-rate
 // FMA polynomials cost about the same VALU time.
 //
-// Coefficients: tools/fit_poly.py (near-minimax least squares on Chebyshev nodes,
-// rounded to f32): |rel err| log1p 1.4e-7, exp2 7.6e-8; |abs err| sin/cos(2 pi r) 8e-8.
+// Coefficients: tools/fit_poly.py (near-minimax least squares on Chebyshev nodes, rounded to f32).
+// Maximum errors of the functions as evaluated in f32, against libm in f64 over their whole input domains
+// (tests/test_math_accuracy.py asserts them; tests/test_gpu_math.py shows the device equals the swept restatement):
+//   log_pos over the 2^23 uniforms u1 = 2 - 1.m: relative 1.661e-7, absolute 5.33e-7
+//   sqrtf(-2 log_pos(u1)), the Box-Muller radius: absolute 3.47e-7
+//   sincos2pi_u24 over all 2^24 j: absolute 8.516e-8 (sin and cos)
+//   exp2_any on the 2^-16 grid over [-126, 127]: relative 7.647e-8
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -100,13 +105,19 @@ __device__ __forceinline__ float exp2_p(float f) {
 }
 
 // 2^y: round-to-nearest-even integer split (v_rndne_f32), polynomial, exact ldexp.
+// Outside [-150, 128]: 0 below -150 for every finite y (the conversion of n saturates) and inf from 128 up, +inf
+// included (n stops at 128, f = y - 128 >= 0, the polynomial is >= 1 or inf); NaN for NaN (fminf drops it, f keeps
+// it) and for -inf (f = inf - inf).
 __device__ __forceinline__ float exp2_any(float y) {
-  const float n = rintf(y);
-  const float f = y - n;  // exact, in [-1/2, 1/2]
+  const float n = rintf(fminf(y, 128.0f));
+  const float f = y - n;  // exact, in [-1/2, 1/2], for y < 128.5
   return ldexpf(exp2_p(f), static_cast<int>(n));
 }
 
 __device__ __forceinline__ float exp_any(float x) { return exp2_any(x * 1.44269502f); }
+
+// The hardware-transcendental natural log of SMC_MATH_HW (the Greeks' log-moneyness): v_log_f32 times ln 2.
+__device__ __forceinline__ float hw_log(float q) { return __builtin_amdgcn_logf(q) * 0.693147182f; }
 
 // ---- f64: twiddles cos/sin(2 pi j / N) of the N-point DFT -------------------------------
 // (sin, cos)(x) for |x| <= pi/4: Taylor series to x^17 / x^18 (truncation < 1e-19)
@@ -154,8 +165,10 @@ __device__ __forceinline__ void twiddle(int64_t j, int64_t N, double& s_out, dou
 // ---- f64 path engine: the Box-Muller transcendentals of 32-bit uniforms and exp ------------
 // Fixed IEEE-754 sequences (fma, +, -, *, exact scaling, frexp and integer bit manipulation) over tables
 // (smc_f64_tables.h: generated in 60-digit decimal arithmetic, rounded to double), restated op for op by
-// oracle/gbm_oracle.c, so f64 normals are bit-identical on the CPU.  Accuracy against libm
-// (tests/test_oracle.py): -2 ln u within 2 ulp, (sin, cos) within 2^-52 absolute, 2^(y/256) within 2 ulp.
+// oracle/gbm_oracle.c, so f64 normals are bit-identical on the CPU (tests/test_gpu_math.py: every function, the
+// frexp / ldexp builtins included, at the edges of its domain and 2^22 random points).  Accuracy against 60-digit
+// and long-double references (tests/test_math_accuracy.py): -2 ln u within 2 ulp (measured 1.04), (sin, cos) within
+// 2^-52 absolute (measured 0.73 2^-52), 2^(y/256) within 2 ulp (measured 1.32; times x: 1.87).
 // The f64 path kernel is VALU-issue-bound (PMC: VALU busy ~88-95 % of the launch, every VALU instruction,
 // integer or f64, 4 cycles per wave), so the forms minimise instructions per path step.  v3 (round 4):
 // -2 ln u directly (the -2 folded into the table and the polynomial as exact power-of-two scalings), its

@@ -103,25 +103,47 @@ struct PathStream {
   //   u1 = 2 - 1.m(a >> 9) in (0, 1]  (exact),  angle = 1.m(b >> 9) revolutions (period 1).
   // HW = false: portable IEEE-only arithmetic (smc_math.h), bit-identical to the CPU oracle:
   //   z = sqrt(-2 ln u1) (cos, sin)(2 pi angle).
-  // HW = true (SMC_MATH_HW): v_log / v_sqrt / v_cos / v_sin_f32 (~1 ulp, not reproducible on
-  //   a CPU), returning sqrt(-log2 u1) (cos, sin) = z / kNormalScale<true>:
+  // HW = true (SMC_MATH_HW): v_log / v_sqrt / v_cos / v_sin_f32 (measured errors: DESIGN.md §3.2; not
+  //   reproducible on a CPU), returning sqrt(-log2 u1) (cos, sin) = z / kNormalScale<true>:
   //   2 alignbit + 1 sub + 4 transcendentals + 2 mul per pair.
+  // The arithmetic is a static function of the two stream words (box_muller), so the test hook
+  // smc_test_math_eval (mathtest.hip) evaluates it at chosen words; normal_pair draws and calls it.
+  static __device__ __forceinline__ float u1_f32(uint32_t a) {
+    return 2.0f - __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, a, 9));
+  }
+
+  // The HW mode's two factors, shared by normal_pair<true>, hw_log_increments4, hw_log_pair (hw_log_tail4)
+  // and the test hook: the radius sqrt(-log2 u1(a)) and (cos, sin) of the angle 1.m(b >> 9) revolutions.
+  static __device__ __forceinline__ float hw_radius(uint32_t a) {
+    return __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(u1_f32(a)));
+  }
+  static __device__ __forceinline__ void hw_cossin(uint32_t b, float& c, float& s) {
+    const float w = __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, b, 9));  // [1, 2) rev
+    c = __builtin_amdgcn_cosf(w);
+    s = __builtin_amdgcn_sinf(w);
+  }
+
   template <bool HW>
-  __device__ __forceinline__ void normal_pair(float& z0, float& z1) {
-    const uint32_t a = next(), b = next();
-    const float u1 = 2.0f - __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, a, 9));
+  static __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
     if constexpr (HW) {
-      const float r = __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(u1));
-      const float w = __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, b, 9));  // [1, 2) rev
-      z0 = r * __builtin_amdgcn_cosf(w);
-      z1 = r * __builtin_amdgcn_sinf(w);
+      const float r = hw_radius(a);
+      float c, s;
+      hw_cossin(b, c, s);
+      z0 = r * c;
+      z1 = r * s;
     } else {
-      const float r = __builtin_sqrtf(-2.0f * math::log_pos(u1));
+      const float r = __builtin_sqrtf(-2.0f * math::log_pos(u1_f32(a)));
       float sn, cs;
       math::sincos2pi_u24((b >> 9) << 1, sn, cs);
       z0 = r * cs;
       z1 = r * sn;
     }
+  }
+
+  template <bool HW>
+  __device__ __forceinline__ void normal_pair(float& z0, float& z1) {
+    const uint32_t a = next(), b = next();
+    box_muller<HW>(a, b, z0, z1);
   }
 
   // HW log-Euler fast path: exponents y = a + b z of the next two steps for the lane's 4 paths
@@ -133,11 +155,8 @@ struct PathStream {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const uint32_t ua = next(), ub = next();
-      const float u1 = 2.0f - __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, ua, 9));
-      r[j] = __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(u1));
-      const float w = __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, ub, 9));
-      c[j] = __builtin_amdgcn_cosf(w);
-      sn[j] = __builtin_amdgcn_sinf(w);
+      r[j] = hw_radius(ua);
+      hw_cossin(ub, c[j], sn[j]);
     }
     const f2 bb = {b, b}, aa = {a, a};
 #pragma unroll
@@ -152,35 +171,45 @@ struct PathStream {
     }
   }
 
+  // One pair of hw_log_tail4 as a function of its words: (y0, y1) = a + (b r) (cos, sin), the same IEEE
+  // operations per element as hw_log_increments4 (one multiply b r, one fma each).
+  static __device__ __forceinline__ void hw_log_pair(uint32_t ua, uint32_t ub, float b, float a, float& y0,
+                                                     float& y1) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const float br = hw_radius(ua) * b;
+    float c, s;
+    hw_cossin(ub, c, s);
+    const f2 v = __builtin_elementwise_fma(f2{br, br}, f2{c, s}, f2{a, a});
+    y0 = v.x;
+    y1 = v.y;
+  }
+
   // HW log-Euler, last step of an odd T: the exponents y = a + b z of the lane's 4 paths from two
   // Box-Muller pairs (paths 0, 1: pair 0's z0, z1; paths 2, 3: pair 1's), the arithmetic of
   // hw_log_increments4.
   __device__ __forceinline__ void hw_log_tail4(float b, float a, float (&y)[4]) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const uint32_t ua = next(), ub = next();
-      const float u1 = 2.0f - __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, ua, 9));
-      const float br = __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(u1)) * b;
-      const float w = __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, ub, 9));
-      const f2 v = __builtin_elementwise_fma(f2{br, br}, f2{__builtin_amdgcn_cosf(w), __builtin_amdgcn_sinf(w)},
-                                             f2{a, a});
-      y[2 * k] = v.x;
-      y[2 * k + 1] = v.y;
+      hw_log_pair(ua, ub, b, a, y[2 * k], y[2 * k + 1]);
     }
   }
 
   // Two N(0,1) draws, double precision: u1 = (a + 1/2) 2^-32 in (0, 1), angle = b 2^-32 revolutions;
   // -2 ln u1 and (sin, cos) of the angle from the 32-bit integers (smc_math.h m2log_u32 / sincos2pi_u32,
   // restated by the CPU oracle: bit-identical normals), sqrt correctly rounded (sqrt_radius).
-  template <bool HW>
-  __device__ __forceinline__ void normal_pair(double& z0, double& z1) {
-    const uint32_t a = next(), b = next();
+  static __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, double& z0, double& z1) {
     const double r = math::sqrt_radius(math::m2log_u32(a));
     double s, c;
     math::sincos2pi_u32(b, s, c);
     z0 = r * c;
     z1 = r * s;
+  }
+
+  template <bool HW>
+  __device__ __forceinline__ void normal_pair(double& z0, double& z1) {
+    const uint32_t a = next(), b = next();
+    box_muller(a, b, z0, z1);
   }
 
   // f64 log-Euler: exponents y = a + (b r) (cos, sin) of the next two steps for the lane's 4 paths (ylo:

@@ -90,7 +90,7 @@ class TrainingEngine:
                              "is not supported")
         _lib.require_device()
         self.math = math
-        # "hw": f32 hardware transcendentals in the path kernel (faster, ~1 ulp, not CPU-reproducible);
+        # "hw": f32 hardware transcendentals in the path kernel (faster, normals within 1.1e-6, not CPU-reproducible);
         # "reference": the reference kernel's typing (f64 state and step, f32 normals and stores: rows_ref_kernel);
         # "reference_hw": the same step on the hardware-transcendental f32 normals (SMC_MATH_REF | SMC_MATH_HW)
         self._scheme = scheme_code(cfg.path_scheme) | {"hw": _lib.MATH_HW, "reference": _lib.MATH_REF,

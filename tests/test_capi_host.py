@@ -42,14 +42,39 @@ def test_library_exports_every_declared_symbol() -> None:
 
 
 def test_test_hooks_are_inert_without_the_environment_switch() -> None:
-    """smc_test_exchange_fault does nothing and fails unless SMC_ENABLE_TEST_HOOKS=1 (a fresh process
-    without it; no GPU call)."""
-    code = ("import ctypes, sys; sys.path.insert(0, %r); from spectralmc_amd import _lib; L = _lib.lib(); "
-            "print(L.smc_test_exchange_fault(1, 5), _lib.last_error())" % os.path.dirname(os.path.dirname(HEADER)))
-    env = {k: v for k, v in os.environ.items() if k != "SMC_ENABLE_TEST_HOOKS"}
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.split()[0] == str(_lib.SMC_ERR_INVALID_ARGUMENT) and "disabled" in out.stdout
+    """smc_test_exchange_fault and smc_test_math_eval do nothing and fail unless SMC_ENABLE_TEST_HOOKS=1 (a fresh
+    process without it, one per entry point so each is the first hook call; no GPU call: the math hook returns
+    before it looks at its pointers)."""
+    calls = ["L.smc_test_exchange_fault(1, 5)",
+             "L.smc_test_math_eval(0, ctypes.addressof(buf), 4, ctypes.addressof(buf), None)"]
+    for call in calls:
+        code = ("import ctypes, sys; sys.path.insert(0, %r); from spectralmc_amd import _lib; L = _lib.lib(); "
+                "buf = (ctypes.c_float * 4)(1, 2, 3, 4); print(%s, _lib.last_error(), list(buf))"
+                % (os.path.dirname(os.path.dirname(HEADER)), call))
+        env = {k: v for k, v in os.environ.items() if k != "SMC_ENABLE_TEST_HOOKS"}
+        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        assert out.stdout.split()[0] == str(_lib.SMC_ERR_INVALID_ARGUMENT) and "disabled" in out.stdout, call
+        assert out.stdout.rstrip().endswith("[1.0, 2.0, 3.0, 4.0]"), call
+
+
+def test_math_hook_argument_errors_do_not_launch() -> None:
+    L = _lib.lib()
+    buf = (ctypes.c_float * 4)(1, 2, 3, 4)
+    p = ctypes.addressof(buf)
+    log_pos = _lib.TEST_MATH["LOG_POS"]
+    assert L.smc_test_math_eval(log_pos, None, 4, p, None) == _lib.SMC_ERR_INVALID_ARGUMENT
+    assert L.smc_test_math_eval(log_pos, p, 4, None, None) == _lib.SMC_ERR_INVALID_ARGUMENT
+    assert L.smc_test_math_eval(len(_lib.TEST_MATH), p, 4, p, None) == _lib.SMC_ERR_INVALID_ARGUMENT
+    assert "function id" in _lib.last_error()
+    assert L.smc_test_math_eval(-1, p, 4, p, None) == _lib.SMC_ERR_INVALID_ARGUMENT
+    assert L.smc_test_math_eval(log_pos, p, -1, p, None) == _lib.SMC_ERR_INVALID_SHAPE
+    assert L.smc_test_math_eval(log_pos, p, 0, p, None) == _lib.SMC_OK
+    assert list(buf) == [1.0, 2.0, 3.0, 4.0]
+    # the ids of the binding are the header's
+    text = open(TESTING_HEADER).read()
+    ids = {name: int(v) for name, v in re.findall(r"SMC_TEST_MATH_([A-Z0-9_]+) = (\d+)", text)}
+    assert ids.pop("COUNT") == len(_lib.TEST_MATH) and ids == _lib.TEST_MATH
 
 
 INTEGRATION = os.path.join(os.path.dirname(HEADER), "..", "INTEGRATION.md")
