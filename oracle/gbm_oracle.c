@@ -295,6 +295,13 @@ void oracle_stream_u32(uint64_t seed, uint64_t ordinal, uint64_t group, int64_t 
   for (int64_t i = 0; i < n; ++i) out[i] = mwc_next(&g);
 }
 
+/* The same words for n_groups consecutive groups from group0 on: out [n_groups][n].  Words only: what a
+ * reference written apart from the kernels may take from here. */
+void oracle_stream_u32_groups(uint64_t seed, uint64_t ordinal, uint64_t group0, int64_t n_groups, int64_t n,
+                              uint32_t* out) {
+  for (int64_t k = 0; k < n_groups; ++k) oracle_stream_u32(seed, ordinal, group0 + (uint64_t)k, n, out + k * n);
+}
+
 /* One Box-Muller pair.  f32: 23-bit uniforms and the portable kernels (bit-identical to the
  * device); f64: 32-bit uniforms and the m2log_u32 / sincos2pi_u32 sequences above (bit-identical). */
 static void box_muller_f32(uint32_t a, uint32_t b, float* z0, float* z1) {

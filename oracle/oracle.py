@@ -56,6 +56,8 @@ def lib() -> ctypes.CDLL:
         L.oracle_philox4x32_10.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.oracle_stream_u32.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64,
                                         ctypes.c_void_p]
+        L.oracle_stream_u32_groups.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_void_p]
         L.oracle_normals.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
                                      ctypes.c_int32, ctypes.c_void_p]
         L.oracle_gbm_paths.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
@@ -112,6 +114,13 @@ def stream_u32(seed: int, ordinal: int, group: int, n: int) -> np.ndarray:
     """The first n u32 outputs of the (seed, ordinal, group) path stream (csrc/smc_rng.h)."""
     out = np.empty(n, dtype=np.uint32)
     lib().oracle_stream_u32(seed, ordinal, group, n, _ptr(out))
+    return out
+
+
+def stream_u32_groups(seed: int, ordinal: int, group0: int, n_groups: int, n: int) -> np.ndarray:
+    """[n_groups, n]: stream_u32 of the groups group0 .. group0 + n_groups - 1 in one call (words only)."""
+    out = np.empty((n_groups, n), dtype=np.uint32)
+    lib().oracle_stream_u32_groups(seed, ordinal, group0, n_groups, n, _ptr(out))
     return out
 
 

@@ -1,10 +1,36 @@
 """Input sets of the device-math tests, shared by the CPU tests of the oracle's restatement
 (tests/test_math_accuracy.py) and the GPU tests of the device functions (tests/test_gpu_math.py), so both sides
-are pinned at the same points.  Pure numpy; no GPU, no oracle."""
+are pinned at the same points, and the accuracy bounds both assert, each named once.  Pure numpy; no GPU, no oracle."""
 
 from __future__ import annotations
 
 import numpy as np
+
+# ---- accuracy bounds ---------------------------------------------------------------------------------------------
+# The maximum errors the sweeps assert, each named once: test_math_accuracy.py (portable, on the CPU restatement) and
+# test_gpu_math.py (SMC_MATH_HW, on the device) assert against these names, and tests/helpers/basket_reference.py
+# builds its a-priori bounds from them, so a bound and the sweep that justifies it cannot drift apart.
+# Portable f32 (fixed IEEE sequences; the measured maxima rounded up in the last digit shown):
+LOG_POS_MAX_REL = 1.67e-7  # log_pos over all 2^23 u1
+LOG_POS_MAX_ABS = 5.4e-7
+RADIUS_MAX_ABS = 3.5e-7  # |sqrtf(-2 log_pos(u1)) - sqrt(-2 ln u1)| over all 2^23 u1
+SINCOS_MAX_ABS = 8.6e-8  # sincos2pi_u24 over all 2^24 angles
+EXP2_MAX_REL = 7.7e-8  # exp2_any on the 2^-16 grid over [-126, 127]
+# SMC_MATH_HW: maxima measured on an MI355X over the whole domain of each factor (the hardware is deterministic per
+# input, so these are the true maxima of this build); the tests assert twice each (the *_BOUND names), which leaves
+# room for a compiler that lowers a builtin through another instruction form and nothing else.
+HW_RADIUS_MAX_ABS = 3.9460e-07  # |kNormalScale r - sqrt(-2 ln u1)| over all 2^23 u1
+HW_SIN_MAX_ABS = 1.2527e-07  # over all 2^23 angles
+HW_COS_MAX_ABS = 1.2527e-07
+HW_EXP2_MAX_REL = 8.1403e-08  # v_exp_f32 on the 2^-16 grid over [-126, 127]
+HW_LOG_MAX_REL = 1.6095e-07  # hw_log over the u1 <= 1/2
+HW_LOG_MAX_ABS = 7.2019e-08  # hw_log over the u1 > 1/2 (ln u1 -> 0)
+HW_RADIUS_BOUND = 2 * HW_RADIUS_MAX_ABS
+HW_SIN_BOUND = 2 * HW_SIN_MAX_ABS
+HW_COS_BOUND = 2 * HW_COS_MAX_ABS
+HW_EXP2_BOUND = 2 * HW_EXP2_MAX_REL
+HW_LOG_REL_BOUND = 2 * HW_LOG_MAX_REL
+HW_LOG_ABS_BOUND = 2 * HW_LOG_MAX_ABS
 
 # ---- portable f32 ------------------------------------------------------------------------------------------------
 

@@ -2,7 +2,9 @@
 restatement (oracle_basket_kernel, in the reduction order of the launch: oracle.basket_order):
 bit-exact in portable math for basket_kernel (+ basket_cf_kernel) and basket_resident_kernel (W = 1
 ... 32 workgroups per contract, the C5 shape included); HW math within the stated north-star
-tolerance; statistics of the correlated drivers; training through GbmCVNNPricer."""
+tolerance; statistics of the correlated drivers; training through GbmCVNNPricer.
+That the kernels and the restatement are right, not only equal: tests/test_gpu_basket_reference.py (an
+independent f64 reference)."""
 
 from __future__ import annotations
 

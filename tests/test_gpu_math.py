@@ -172,15 +172,8 @@ def test_sqrt_radius_is_correctly_rounded(oracle) -> None:
 
 
 # ---- SMC_MATH_HW: hardware transcendentals against f64 references of the exact inputs ------------------------------------
-# Maxima measured on an MI355X over the whole domain of each factor (the hardware is deterministic per input, so these
-# are the true maxima of this build); the tests assert twice each, which leaves room for a compiler that lowers a builtin
-# through another instruction form and nothing else.
-HW_RADIUS_MAX_ABS = 3.9460e-07  # |kNormalScale r - sqrt(-2 ln u1)| over all 2^23 u1
-HW_SIN_MAX_ABS = 1.2527e-07  # over all 2^23 angles
-HW_COS_MAX_ABS = 1.2527e-07
-HW_EXP2_MAX_REL = 8.1403e-08  # v_exp_f32 on the 2^-16 grid over [-126, 127]
-HW_LOG_MAX_REL = 1.6095e-07  # hw_log over the u1 <= 1/2
-HW_LOG_MAX_ABS = 7.2019e-08  # hw_log over the u1 > 1/2 (ln u1 -> 0)
+# The measured maxima HW_*_MAX_* and the asserted bounds HW_*_BOUND (twice each) are named in
+# tests/helpers/math_inputs.py.
 NORMAL_TOL = 2e-5  # the project's bound on an SMC_MATH_HW normal (test_hw_math_mode_within_fp32_tolerance)
 MAX_RADIUS = 5.6468  # >= sqrt(46 ln 2), the radius at u1 = 2^-23
 
@@ -242,11 +235,11 @@ def test_hw_factor_maxima(hw_factors) -> None:
     assert hw_factors["cos"][0] == 1.0 and hw_factors["sin"][0] == 0.0
     assert [float(hw_factors["radius"][mi.a_of_u1(2.0**-e) >> 9]) for e in (1, 4, 16)] == [1.0, 2.0, 4.0]
     assert hw_factors["radius"][0] == 0.0  # u1 = 1: sqrt(-0)
-    assert dr.max() <= 2 * HW_RADIUS_MAX_ABS
-    assert ds.max() <= 2 * HW_SIN_MAX_ABS
-    assert dc.max() <= 2 * HW_COS_MAX_ABS
+    assert dr.max() <= mi.HW_RADIUS_BOUND
+    assert ds.max() <= mi.HW_SIN_BOUND
+    assert dc.max() <= mi.HW_COS_BOUND
     # the per-factor constants compose to the project's bound on a normal: |dz| <= |dr| |trig| + r |dtrig|
-    assert HW_RADIUS_MAX_ABS + MAX_RADIUS * max(HW_SIN_MAX_ABS, HW_COS_MAX_ABS) < NORMAL_TOL
+    assert mi.HW_RADIUS_MAX_ABS + MAX_RADIUS * max(mi.HW_SIN_MAX_ABS, mi.HW_COS_MAX_ABS) < NORMAL_TOL
 
 
 @pytest.mark.parametrize("a,b", _hw_sweeps())
@@ -305,6 +298,6 @@ def test_hw_exp2_and_log_maxima() -> None:
     print(f"HW_LOG max rel (u1 <= 1/2) {lrel.max():.4e}; max abs (u1 > 1/2) {labs.max():.4e}")
     assert not np.isnan(e).any() and not np.isnan(lg).any()
     assert lg[0] == 0.0  # ln 1
-    assert rel.max() <= 2 * HW_EXP2_MAX_REL
-    assert lrel.max() <= 2 * HW_LOG_MAX_REL
-    assert labs.max() <= 2 * HW_LOG_MAX_ABS
+    assert rel.max() <= mi.HW_EXP2_BOUND
+    assert lrel.max() <= mi.HW_LOG_REL_BOUND
+    assert labs.max() <= mi.HW_LOG_ABS_BOUND

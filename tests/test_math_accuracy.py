@@ -5,8 +5,8 @@ the restatement bit for bit over the same inputs.  CPU only.
 The portable f32 functions are fixed sequences of IEEE operations, so their maximum errors are constants of the
 code: the bounds below are the maxima measured against libm in f64 (log_pos: relative 1.661e-7, absolute 5.33e-7;
 radius 3.47e-7; sin / cos 8.516e-8; exp2 7.647e-8), rounded up in the last digit shown.  A coefficient change has to
-move them deliberately.  The f64 functions keep the bounds of test_oracle.py's sampled test (2 ulp; 2^-52 absolute
-for sin / cos), now at the structured points of tests/helpers/math_inputs.py against mpmath (60 digits) and at 2^22
+move them deliberately (each is named once, in tests/helpers/math_inputs.py).  The f64 functions keep the bounds of
+test_oracle.py's sampled test (2 ulp; 2^-52 absolute for sin / cos), now at the structured points of tests/helpers/math_inputs.py against mpmath (60 digits) and at 2^22
 random points against numpy long double (an f64 libm reference of x 2^(ys/256) carries up to 1.5 ulp of its own)."""
 
 from __future__ import annotations
@@ -29,14 +29,14 @@ def test_log_pos_over_every_uniform(oracle) -> None:
     nz = want != 0.0
     rel, ab = float((err[nz] / np.abs(want[nz])).max()), float(err.max())
     print(f"log_pos: max relative {rel:.4e}, max absolute {ab:.4e}")
-    assert rel <= 1.67e-7
-    assert ab <= 5.4e-7
+    assert rel <= mi.LOG_POS_MAX_REL
+    assert ab <= mi.LOG_POS_MAX_ABS
     # the Box-Muller radius as box_muller<false> forms it: sqrtf(-2 log_pos(u1))
     radius = np.sqrt(F32(-2.0) * got)
     assert radius.dtype == np.float32
     rerr = float(np.abs(radius.astype(np.float64) - np.sqrt(-2.0 * want)).max())
     print(f"radius: max absolute {rerr:.4e}")
-    assert rerr <= 3.5e-7
+    assert rerr <= mi.RADIUS_MAX_ABS
     assert got[0] == 0.0 and not np.signbit(got[0])  # log_pos(1.0f) == +0.0f exactly
     assert np.all(got[1:] < 0.0)
 
@@ -48,7 +48,7 @@ def test_sincos2pi_u24_over_every_angle(oracle) -> None:
     es = float(np.abs(sc[:, 0] - np.sin(ang)).max())
     ec = float(np.abs(sc[:, 1] - np.cos(ang)).max())
     print(f"sincos2pi_u24: max absolute sin {es:.4e}, cos {ec:.4e}")
-    assert es <= 8.6e-8 and ec <= 8.6e-8
+    assert es <= mi.SINCOS_MAX_ABS and ec <= mi.SINCOS_MAX_ABS
     # the four quarter turns are exact (and j = 2^24, the k = 4 branch of the reduction, is the turn again)
     q = oracle.sincos2pi_u24_n(np.array([0, 1 << 22, 1 << 23, 3 << 22, 1 << 24], dtype=np.uint32))
     np.testing.assert_array_equal(q, np.array([[0, 1], [1, 0], [0, -1], [-1, 0], [0, 1]], dtype=np.float32))
@@ -63,7 +63,7 @@ def test_exp2_any_grid_and_edges(oracle) -> None:
     want = np.exp2(y.astype(np.float64))
     rel = float((np.abs(got - want) / want).max())
     print(f"exp2_any: max relative {rel:.4e}")
-    assert rel <= 7.7e-8
+    assert rel <= mi.EXP2_MAX_REL
     # integers: exact powers of two over the whole finite range, subnormal results included
     k = np.arange(-149, 128)
     np.testing.assert_array_equal(oracle.exp2_n(k.astype(F32)), np.ldexp(F32(1.0), k).astype(F32))
@@ -72,7 +72,7 @@ def test_exp2_any_grid_and_edges(oracle) -> None:
     normal = t >= -126
     tie = oracle.exp2_n(t).astype(np.float64)
     want_t = np.exp2(t.astype(np.float64))
-    assert float((np.abs(tie - want_t) / want_t)[normal].max()) <= 7.7e-8
+    assert float((np.abs(tie - want_t) / want_t)[normal].max()) <= mi.EXP2_MAX_REL
     n = np.rint(t)
     assert set(np.unique(t - n)) == {-0.5, 0.5}
     # subnormal results: the polynomial's value rounded once by ldexpf, so within half a subnormal ulp (2^-150)
@@ -80,7 +80,7 @@ def test_exp2_any_grid_and_edges(oracle) -> None:
     ys = mi.exp2_subnormal()
     sub = oracle.exp2_n(ys).astype(np.float64)
     want_s = np.exp2(ys.astype(np.float64))
-    assert np.all(np.abs(sub - want_s) <= 2.0**-150 + 7.7e-8 * want_s)
+    assert np.all(np.abs(sub - want_s) <= 2.0**-150 + mi.EXP2_MAX_REL * want_s)
     assert np.all((sub > 0) & (sub < 2.0**-126))
     assert np.all(np.diff(sub) >= 0)
     # out of range, finite: 0 below -150, inf from 128 up; the float -> int conversion saturates as the device's does
@@ -108,7 +108,7 @@ def test_exp2_any_of_plus_infinity_is_infinity(oracle) -> None:
     got = oracle.exp2_n(y)
     np.testing.assert_array_equal(got[3:], np.full(6, np.inf, dtype=F32))
     want = np.exp2(y[:3].astype(np.float64))
-    assert np.all(np.abs(got[:3].astype(np.float64) - want) <= 7.7e-8 * want)
+    assert np.all(np.abs(got[:3].astype(np.float64) - want) <= mi.EXP2_MAX_REL * want)
 
 
 def test_exp_any_is_exp2_any_of_the_scaled_argument(oracle) -> None:
