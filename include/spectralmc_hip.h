@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 19  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks */
+#define SMC_ABI_VERSION 20  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -516,8 +516,8 @@ const char* smc_basket_price_kernel(int32_t n_assets, int32_t timesteps, int64_t
  * flag; SMC_MATH_REF; SMC_MATH_HW with f64; bad normalization), then the simple-Euler rejection.
  * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  Contract values are not
  * validated on the device, as elsewhere: X0 <= 0 gives NaN.  B below the CU count leaves CUs idle.
- * Out of scope: simple Euler; Greeks of the path-dependent and basket payoffs; likelihood-ratio or
- * second-order pathwise gamma; cross-Greeks. */
+ * Out of scope: simple Euler; Greeks of the path-dependent payoffs (the equal-weight basket's are
+ * smc_basket_greeks, below); likelihood-ratio or second-order pathwise gamma; cross-Greeks. */
 #define SMC_GREEKS_COLS 26
 int32_t smc_gbm_greeks(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
                        uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
@@ -526,6 +526,86 @@ int32_t smc_gbm_greeks(const double* contracts_dev, int64_t n_contracts, int32_t
  * rejects, simple Euler among them).  Static string, no device call. */
 const char* smc_gbm_greeks_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
                                   int32_t dtype);
+
+/* ---- batched basket Greeks (ABI 20) ---------------------------------------------
+ * Pathwise sensitivities of the equal-weight basket put and call smc_basket_price averages, for B contracts of
+ * A assets in ONE launch: the price call's workgroup per contract (512 lanes), contract rows ([B][3A+4]: K, T, r,
+ * rho, X0[A], d[A], v[A]), streams (contract b uses ordinal (*ordinal_dev or 0) + ordinal0 + b), Cholesky factor,
+ * packed f32 step, chunk and validity handling (any n_paths >= 1) and fixed sum orders, so the block is bit-identical
+ * run to run, under any split of the batch, with the ordinal on the host or on the device, and in the lds and replay
+ * modes.  The A terminal values x_i of a path give its log returns L_i = log(x_i / X0_i) = mu_i T + v_i W_i and
+ * with them every derivative below; the estimators are the derivatives of the estimator smc_basket_price
+ * computes, including, under SMC_NORM_NORMALIZE, the dependence of the scales F_i / mean(x_i) on the parameter.
+ * Per contract, each constant in f64 from the row (every f64 operation rounded, in the order written), then
+ * rounded to f32:
+ *   K, df, F_i, s_i, wA   exactly smc_basket_price's (s_i = F_i / f32(tot_i / P) under NORMALIZE, 1 under RAW)
+ *   mu_i = r - d_i - 0.5 v_i v_i    ix0_i = f32(1 / X0_i)    cv_i = f32(1 / v_i), 0 if v_i == 0
+ *   cT = f32(1 / (2 T)), 0 if T == 0    crho = df * (f32(T) * K)    rr = f32(r)
+ *   Lc   the engine's Banachiewicz factor of (1 - rho) I + rho 11^T (f64)
+ *   dL   its derivative in rho, statement by statement: for i, for k <= i: ds = (i == k ? 0 : 1), then for m < k:
+ *        ds = ds - (dL_im Lc_km + Lc_im dL_km);  dL_ii = ds / (2 Lc_ii),  dL_ik = (ds - Lc_ik dL_kk) / Lc_kk
+ *   G    = dL Lc^-1 (lower triangular), row i from k = i down to 0: g = dL_ik, then for m = k + 1 .. i:
+ *        g = g - G_im Lc_mk;  G_ik = g / Lc_kk.  dW / drho = G W for the correlated Brownian sums W = Lc (driver sums).
+ *   g_ik = f32(v_i G_ik / v_k) for k <= i
+ *   g0_i = f32(-(v_i gs_i)), gs_i = sum_{k <= i} G_ik mu_k T / v_k (from 0, in k order)
+ *        (any v_k == 0: every g_ik and g0_i is 0, see the conventions)
+ *   RAW:        av_i = f32(-mu_i T / v_i - v_i T), 0 if v_i == 0    aT_i = f32(mu_i / 2)    ac_i = 0
+ *   NORMALIZE:  Lbar_i = sxl_i / tot_i (f64)    av_i = f32(-Lbar_i / v_i), 0 if v_i == 0
+ *               aT_i = f32(-Lbar_i / (2 T) + (r - d_i)), f32(r - d_i) if T == 0    ac_i = f32(-sxc_i / tot_i)
+ * Per path, all in f32, every operation rounded (no fused multiply-add):
+ *   L_i = log(x_i / f32(X0_i))  (the portable f32 log; v_log_f32 times ln 2 under SMC_MATH_HW)
+ *   c_i = (..((g0_i + g_i0 L_0) + g_i1 L_1) ..) + g_ii L_i     (v_i times d W_i / d rho)
+ *   xs_i = x_i s_i    bk = (((0 + xs_0) + xs_1) + ...) wA    ip = K - bk > 0    ic = bk - K > 0
+ *   put = df max(K - bk, 0)    call = df max(bk - K, 0)    w_i = (df * xs_i) * wA
+ *   hv_i = L_i * cv_i + av_i    hT_i = L_i * cT + aT_i    hc_i = c_i + ac_i
+ *   sT = ((0 + w_0 * hT_0) + w_1 * hT_1) + ...    sC = ((0 + w_0 * hc_0) + w_1 * hc_1) + ...
+ *   delta_i      put: ip ? -(w_i * ix0_i) : 0     call: ic ? w_i * ix0_i : 0       (d / d X0_i)
+ *   vega_i       put: ip ? -(w_i * hv_i) : 0      call: ic ? w_i * hv_i : 0        (d / d v_i)
+ *   rho          put: ip ? -crho : 0              call: ic ? crho : 0              (d / d r)
+ *   theta        put: rr * put + (ip ? sT : 0)    call: rr * call - (ic ? sT : 0)  (-d / d T, per year)
+ *   correlation  put: ip ? -sC : 0                call: ic ? sC : 0                (d / d rho of the equicorrelation)
+ * each cast to f64 and added with its square (f64); a column's sum runs per lane over its chunks and paths in
+ * order, then the wave butterfly, then waves 0..7.
+ * greeks_dev [B][2n + 4], n = 4A + 6:
+ *   0 .. A-1 / A .. 2A-1 delta put / call      2A .. 3A-1 / 3A .. 4A-1 vega put / call
+ *   4A, 4A+1 rho put / call    4A+2, 4A+3 theta put / call    4A+4, 4A+5 correlation put / call
+ *   n .. 2n-1 the standard errors of columns 0 .. n-1 (the price call's formula; 0 at P = 1)
+ *   2n, 2n+1 put / call price: smc_basket_price's columns 0 and 1 bit for bit
+ *   2n+2, 2n+3 their standard errors: smc_basket_price's columns 6 and 7 bit for bit.
+ * sums_dev (may be NULL) [B][3][A] f64: tot_i (smc_basket_price's terminal_sum_dev bit for bit), then
+ * sxl_i = sum_p f64(x_i * L_i) and sxc_i = sum_p f64(x_i * c_i) (NORMALIZE; both 0 under RAW; the columns' sum order).
+ * Conventions: v_i == 0 gives vega_i = 0 and its error 0.  Any v_i == 0 with A > 1: the drivers cannot be recovered
+ * from a deterministic asset, so the four correlation columns (values and errors) are written as NaN, computed
+ * with g = g0 = 0 (sxc = 0).  A == 1: there is no correlation, G = 0 and the correlation columns are exactly 0
+ * (also at v == 0).  T == 0 drops the cT term.  P == 1 gives every standard error 0.  The standard errors take the P
+ * terms as independent (they leave out the sampling error of the shared s_i, Lbar_i and ac_i).  Contract values are
+ * not validated otherwise: at a singular matrix (rho = 1) the correlation columns and sxc may be non-finite, the
+ * rest stays finite for A <= 2.
+ * Modes: RAW takes the sums as the paths finish.  NORMALIZE needs the terminal values again once tot, sxl and sxc are
+ * known: parked in LDS (x only; L and c are recomputed from the same bits) while A * roundup4(P) * 4 bytes and 6848
+ * bytes of scratch fit in 144 KiB, else simulated again; SMC_PRICE_REPLAY forces the latter.  For A <= 4 all 4A + 8
+ * sums are taken in one payoff pass; for A = 5..8 the registers do not hold them beside the path loop, so the columns
+ * are taken 8 per-path terms at a time (terms in column order, the prices last) in ceil((4A + 8) / 8) payoff passes,
+ * after a pass for tot alone and (NORMALIZE) one for sxl and sxc, each over the parked values, or over paths simulated
+ * again (replay, and RAW too): the same values and each column's one order in every mode.
+ * math: 0 (portable, CPU-reproducible) or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY; any other bit is rejected.
+ * Checks, in smc_basket_price's order and all before the empty batch (n_contracts = 0: SMC_OK, nothing touched) is
+ * accepted.  SMC_ERR_INVALID_ARGUMENT: NULL contracts_dev, NULL greeks_dev, n_assets outside 1..8, bad math, bad
+ * normalization.  SMC_ERR_INVALID_SHAPE: n_contracts < 0 or >= 2^31, timesteps <= 0, n_paths <= 0 or >= 2^40.
+ * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  B below the CU count leaves CUs idle.
+ * Out of scope: Greeks of the best-of / worst-of payoffs; gammas and cross-gammas (no diagonal lognormal identity
+ * holds for a basket); caller weights and general correlation matrices; a float64 basket engine; likelihood-ratio
+ * estimators. */
+int32_t smc_basket_greeks(const double* contracts_dev /*[B][3A+4]*/, int64_t n_contracts, int32_t n_assets,
+                          int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                          int64_t ordinal0, int32_t math, int32_t normalization,
+                          double* greeks_dev /*[B][8A+16]*/, double* sums_dev /*[B][3A] or NULL*/, void* stream);
+/* "basket_greeks_kernel(raw)", "basket_greeks_kernel(lds)", "basket_greeks_kernel(replay)" or "unsupported" (a
+ * call smc_basket_greeks rejects).  Static string, no device call. */
+const char* smc_basket_greeks_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                     int32_t normalization);
+/* Doubles per contract of greeks_dev: 8 n_assets + 16; -1 for n_assets outside 1..8. */
+int32_t smc_basket_greeks_cols(int32_t n_assets);
 
 #ifdef __cplusplus
 }

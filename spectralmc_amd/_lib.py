@@ -45,7 +45,7 @@ PRICE_COLS = 8  # doubles per contract smc_gbm_price writes
 PATH_PRICE_COLS = 20  # doubles per contract smc_gbm_price_paths writes
 BASKET_PRICE_COLS = 18  # doubles per contract smc_basket_price writes
 GREEKS_COLS = 26  # doubles per contract smc_gbm_greeks writes
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _c_i32, _c_i64, _c_u64, _c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
 
@@ -107,6 +107,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_basket_price": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
                                   _c_vp, _c_vp]),
     "smc_basket_price_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i32]),
+    "smc_basket_greeks": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
+                                   _c_vp, _c_vp]),
+    "smc_basket_greeks_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i32]),
+    "smc_basket_greeks_cols": (_c_i32, [_c_i32]),
 }
 
 # include/spectralmc_hip_testing.h: test-only entry points, inert unless SMC_ENABLE_TEST_HOOKS=1
@@ -194,6 +198,14 @@ def lib() -> ctypes.CDLL:
                 raise HipExtensionMissing(f"{LIB_PATH}: ABI {handle.smc_abi_version()} != {ABI_VERSION}")
             _lib = handle
     return _lib
+
+
+def basket_greeks_cols(n_assets: int) -> int:
+    """Doubles per contract smc_basket_greeks writes for this asset count: 8 A + 16 (smc_basket_greeks_cols)."""
+    n = int(lib().smc_basket_greeks_cols(n_assets))
+    if n < 0:
+        raise ValueError(f"n_assets must be in 1..8, got {n_assets}")
+    return n
 
 
 def last_error() -> str:

@@ -19,7 +19,8 @@ record the network, optimizer and Sobol/normal positions as usual but not the ba
 configuration: call ``use_basket_engine`` again on the restored pricer.  ``predict_price``
 stays single-asset; the Monte-Carlo price of a basket (and of the best-of / worst-of payoffs on the
 same paths) comes from ``basket_price`` / ``BasketEngine.price``: one launch of ``smc_basket_price`` for
-B contracts, no terminal buffer in memory.
+B contracts, no terminal buffer in memory.  ``basket_greeks`` / ``BasketEngine.greeks`` give the basket put's and
+call's per-asset deltas and vegas, rho, theta and correlation sensitivity the same way (``smc_basket_greeks``).
 """
 
 from __future__ import annotations
@@ -209,6 +210,95 @@ def basket_price(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 
                         block=block)
 
 
+def basket_greeks_fields(n_assets: int) -> tuple[str, ...]:
+    """The names of ``smc_basket_greeks``'s 8A + 16 columns in order: per-asset ``delta_put_i``, ``delta_call_i``,
+    ``vega_put_i``, ``vega_call_i``, then ``rho_put``, ``rho_call``, ``theta_*``, ``correlation_*``, the same names with
+    ``_stderr``, and ``put``, ``call``, ``put_stderr``, ``call_stderr``."""
+    if not 1 <= n_assets <= MAX_ASSETS:
+        raise ValueError(f"n_assets must be in 1..{MAX_ASSETS}, got {n_assets}")
+    means = tuple(f"{kind}_{side}_{i}" for kind in ("delta", "vega") for side in ("put", "call") for i in range(n_assets))
+    means += tuple(f"{kind}_{side}" for kind in ("rho", "theta", "correlation") for side in ("put", "call"))
+    return means + tuple(m + "_stderr" for m in means) + ("put", "call", "put_stderr", "call_stderr")
+
+
+@dataclass(frozen=True)
+class BasketGreeks:
+    """``smc_basket_greeks``'s block for B contracts of A assets.  Every field but the three sums is a view of
+    ``block`` [B, 8A + 16] (``basket_greeks_fields`` order): per-asset deltas and vegas [B, A], rho, theta (-dV/dT per
+    year) and the sensitivity to the equicorrelation parameter [B], their standard errors, and the basket put and
+    call prices with theirs (``smc_basket_price``'s columns 0, 1, 6, 7 bit for bit).  ``terminal_sum``, ``sum_xl``
+    and ``sum_xc`` [B, A] are the pass-1 sums (the last two 0 under RAW)."""
+    delta_put: torch.Tensor
+    delta_call: torch.Tensor
+    vega_put: torch.Tensor
+    vega_call: torch.Tensor
+    rho_put: torch.Tensor
+    rho_call: torch.Tensor
+    theta_put: torch.Tensor
+    theta_call: torch.Tensor
+    correlation_put: torch.Tensor
+    correlation_call: torch.Tensor
+    delta_put_stderr: torch.Tensor
+    delta_call_stderr: torch.Tensor
+    vega_put_stderr: torch.Tensor
+    vega_call_stderr: torch.Tensor
+    rho_put_stderr: torch.Tensor
+    rho_call_stderr: torch.Tensor
+    theta_put_stderr: torch.Tensor
+    theta_call_stderr: torch.Tensor
+    correlation_put_stderr: torch.Tensor
+    correlation_call_stderr: torch.Tensor
+    put: torch.Tensor
+    call: torch.Tensor
+    put_stderr: torch.Tensor
+    call_stderr: torch.Tensor
+    terminal_sum: torch.Tensor
+    sum_xl: torch.Tensor
+    sum_xc: torch.Tensor
+    block: torch.Tensor
+
+
+def _greeks_views(block: torch.Tensor, A: int) -> dict[str, torch.Tensor]:
+    """The named views of a [B, 8A + 16] block (the column table of include/spectralmc_hip.h)."""
+    n = 4 * A + 6
+    out: dict[str, torch.Tensor] = {}
+    for suffix, base in (("", 0), ("_stderr", n)):
+        for j, name in enumerate(("delta_put", "delta_call", "vega_put", "vega_call")):
+            out[name + suffix] = block[:, base + j * A:base + (j + 1) * A]
+        for j, name in enumerate(("rho_put", "rho_call", "theta_put", "theta_call", "correlation_put",
+                                  "correlation_call")):
+            out[name + suffix] = block[:, base + 4 * A + j]
+    for j, name in enumerate(("put", "call", "put_stderr", "call_stderr")):
+        out[name] = block[:, 2 * n + j]
+    return out
+
+
+def basket_greeks(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 0, n_paths: int | None = None,
+                  replay: bool = False) -> BasketGreeks:
+    """Pathwise Greeks of the equal-weight basket put and call of device contracts [B, 3A+4] f64: one launch of
+    ``smc_basket_greeks`` on the current stream, no host synchronisation.  Arguments as ``basket_price``."""
+    if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
+            not contracts.is_contiguous():
+        raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
+    P = cfg.total_paths if n_paths is None else int(n_paths)
+    if P <= 0:
+        raise ValueError(f"n_paths must be positive, got {n_paths}")
+    _lib.require_device()
+    if not contracts.is_cuda:
+        raise ValueError("contracts must be a device tensor")
+    B, A = contracts.shape[0], cfg.n_assets
+    block = torch.empty((B, _lib.basket_greeks_cols(A)), dtype=torch.float64, device=contracts.device)
+    sums = torch.empty((B, 3, A), dtype=torch.float64, device=contracts.device)
+    if B > 0:
+        math = (_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0)
+        _lib.check(_lib.lib().smc_basket_greeks(
+            _lib.ptr(contracts), B, A, cfg.timesteps, P, cfg.mc_seed, None, ordinal0, math,
+            _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW, _lib.ptr(block), _lib.ptr(sums),
+            _lib.stream_handle()))
+    return BasketGreeks(**_greeks_views(block, A), terminal_sum=sums[:, 0], sum_xl=sums[:, 1], sum_xc=sums[:, 2],
+                        block=block)
+
+
 class BasketEngine:
     """Device buffers + launches of the basket Monte-Carlo side of one training step
     (the ``TrainingEngine`` interface)."""
@@ -320,6 +410,13 @@ class BasketEngine:
         return basket_price(self.buffers.contracts if contracts is None else contracts, self.cfg, ordinal0=ordinal0,
                             n_paths=n_paths)
 
+    def greeks(self, contracts: torch.Tensor | None = None, *, ordinal0: int = 0,
+               n_paths: int | None = None) -> BasketGreeks:
+        """Pathwise Greeks (``basket_greeks``) with the engine's configuration, by default of the contracts of the
+        last enqueued step."""
+        return basket_greeks(self.buffers.contracts if contracts is None else contracts, self.cfg, ordinal0=ordinal0,
+                             n_paths=n_paths)
+
 
 def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) -> None:
     """Make ``pricer`` train on basket contracts: its training sessions build a ``BasketEngine``
@@ -331,5 +428,6 @@ def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) ->
     pricer.mc_engine_factory = factory
 
 
-__all__ = ["BasketConfig", "BasketEngine", "BasketPrices", "basket_fields", "basket_price", "basket_targets",
-           "default_basket_bounds", "use_basket_engine", "MAX_ASSETS"]
+__all__ = ["BasketConfig", "BasketEngine", "BasketGreeks", "BasketPrices", "basket_fields", "basket_greeks",
+           "basket_greeks_fields", "basket_price", "basket_targets", "default_basket_bounds", "use_basket_engine",
+           "MAX_ASSETS"]

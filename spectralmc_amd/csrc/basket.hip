@@ -27,6 +27,8 @@
 // in portable math.
 
 #include <cmath>
+#include <type_traits>
+#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -544,6 +546,408 @@ __global__ __launch_bounds__(kBThreads) void basket_price_kernel(BasketArgs a, d
     const float ip = Kf - fs * wA, ic = fs * wA - Kf;
     out[16] = static_cast<double>(df * (ip > 0.0f ? ip : 0.0f));
     out[17] = static_cast<double>(df * (ic > 0.0f ? ic : 0.0f));
+  }
+}
+
+// ---- batched basket Greeks: basket_greeks_kernel (smc_basket_greeks) -----------------------------
+// basket_price_kernel's geometry, streams, chunk / validity handling, modes and sum orders (restated, not
+// shared: basket_price_kernel's registers stay as they are; the path loop is basket_lane_paths, which only the
+// price kernel and this one call).  The A terminal values of a path give its log returns L_i = log(x_i / X0_i)
+// and, through G = (dLc / drho) Lc^-1, the derivative c_i of asset i's correlated Brownian sum with respect to
+// the equicorrelation parameter: every pathwise derivative of the equal-weight basket put and call follows (the
+// table of include/spectralmc_hip.h).  NT = 4A + 8 per-path f32 terms (delta and vega per asset,
+// rho, theta, correlation, price; put and call), each cast to f64 and added with its square.
+// Registers: 2 NT f64 accumulators per lane do not fit beside the path loop from A = 5 on, so the terms are
+// taken basket_greek_pass_terms(A) at a time in payoff passes over the parked (lds) or re-simulated (raw,
+// replay) values, after a pass for the terminal sums alone and (NORMALIZE) one for sxl and sxc; a sum belongs to
+// one pass, so it keeps its one order and lds and replay stay bit-identical.  The per-asset constants of the table live in LDS as f32 (written once per contract by the
+// threads below A, read back by every lane), not in registers.
+constexpr int basket_greek_terms(int A) { return 4 * A + 8; }
+constexpr int basket_greek_pass_terms(int A) { return A <= 4 ? basket_greek_terms(A) : 8; }
+constexpr int kBGreekRed = 2 * basket_greek_terms(4);  // the widest pass: 24 terms and their squares
+constexpr int kBGreekFc = 8;                           // f32 constants per asset: s, ix0, cv, av, aT, ac, g0
+// scratch at the head of the dynamic LDS (f64): pass-sum partials [kBWaves][kBGreekRed], Lc, dLc / drho and G
+// [8][8] each, pass-1 partials [kBWaves][3][8] and totals [3][8] (tot, sxl, sxc), then the f32 constants
+// [8][kBGreekFc] and g [8][8] (6848 B, a multiple of 16)
+constexpr int kBGreekHead = kBWaves * kBGreekRed + 3 * kMaxAssets * kMaxAssets + kBWaves * 3 * kMaxAssets +
+                            3 * kMaxAssets + (kMaxAssets * kBGreekFc + kMaxAssets * kMaxAssets) / 2;
+constexpr size_t kBGreekScratch = kBGreekHead * sizeof(double);
+
+// d Lc / d rho of the Banachiewicz recursion of cholesky_equicorr (the derivative of each of its statements, in
+// its order), then G = dLc Lc^-1 row by row from the last column (G Lc = dLc; G is lower triangular).  f64, one
+// thread, matrices in LDS with row stride 8.
+__device__ void cholesky_equicorr_drho(int A, const double* L, double* dL, double* G) {
+  for (int i = 0; i < A; ++i)
+    for (int k = 0; k <= i; ++k) {
+      double ds = i == k ? 0.0 : 1.0;
+      for (int m = 0; m < k; ++m)
+        ds = ds - (dL[i * kMaxAssets + m] * L[k * kMaxAssets + m] + L[i * kMaxAssets + m] * dL[k * kMaxAssets + m]);
+      dL[i * kMaxAssets + k] = i == k ? ds / (2.0 * L[i * kMaxAssets + i])
+                                      : (ds - L[i * kMaxAssets + k] * dL[k * kMaxAssets + k]) / L[k * kMaxAssets + k];
+    }
+  for (int i = 0; i < A; ++i)
+    for (int k = i; k >= 0; --k) {
+      double g = dL[i * kMaxAssets + k];
+      for (int m = k + 1; m <= i; ++m) g = g - G[i * kMaxAssets + m] * L[m * kMaxAssets + k];
+      G[i * kMaxAssets + k] = g / L[k * kMaxAssets + k];
+    }
+}
+
+template <bool HW>
+__device__ __forceinline__ float basket_greeks_log(float x, float x0) {
+  const float q = x / x0;
+  if constexpr (HW) return math::hw_log(q);
+  else return math::log_pos(q);
+}
+
+template <int... I, typename F>
+__device__ __forceinline__ void basket_static_for(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+
+template <int A, bool HW, int MODE>
+__global__ __launch_bounds__(kBThreads) void basket_greeks_kernel(BasketArgs a, double* __restrict__ greeks,
+                                                                  double* __restrict__ sums) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  constexpr int NT = basket_greek_terms(A);       // per-path terms
+  constexpr int TP = basket_greek_pass_terms(A);  // terms per payoff pass
+  constexpr int NP = (NT + TP - 1) / TP;          // payoff passes
+  constexpr int NG = NT - 2;                      // Greek columns n = 4A + 6
+  extern __shared__ double lds[];  // kBGreekHead doubles of scratch, then (kBPriceLds) the parked block
+  double* Ld = lds + kBWaves * kBGreekRed;        // [8][8]
+  double* dLd = Ld + kMaxAssets * kMaxAssets;     // [8][8]
+  double* Gd = dLd + kMaxAssets * kMaxAssets;     // [8][8]
+  double* wsum = Gd + kMaxAssets * kMaxAssets;    // [kBWaves][3][8]
+  double* tot = wsum + kBWaves * 3 * kMaxAssets;  // [3][8]: tot, sxl, sxc
+  float* fc = reinterpret_cast<float*>(tot + 3 * kMaxAssets);  // [8][kBGreekFc]
+  float* gk = fc + kMaxAssets * kBGreekFc;        // [8][8]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  const int64_t P4 = (P + 3) & ~int64_t{3};  // the parked block's row length
+  v4f* park = reinterpret_cast<v4f*>(lds + kBGreekHead);
+
+  const double* c = a.contracts + b * (3 * A + 4);
+  const double Tm = c[1], r = c[2], rho = c[3];
+  if (tid == 0) {
+    cholesky_equicorr(A, rho, Ld);
+    cholesky_equicorr_drho(A, Ld, dLd, Gd);
+  }
+  __syncthreads();
+  // per-asset log2-unit coefficients, as basket_kernel
+  const double dt = Tm / static_cast<double>(T);
+  const double sq = sqrt(dt);
+  constexpr double zscale = HW ? PathStream::kNormalScale<true> : 1.0;
+  float ca[A], x0[A], Lb[A][A];
+  bool anyv0 = false;
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double drift = r - d - 0.5 * v * v;
+    ca[i] = static_cast<float>(drift * dt * kBLog2e);
+    const double bi = v * sq * kBLog2e * zscale;
+    x0[i] = static_cast<float>(c[4 + i]);
+    anyv0 = anyv0 || v == 0.0;
+#pragma unroll
+    for (int k = 0; k < A; ++k) Lb[i][k] = k <= i ? static_cast<float>(bi * Ld[i * kMaxAssets + k]) : 0.0f;
+  }
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+
+  // payoff constants (basket_price_kernel's) and the scalar constants of the table
+  const float Tf = static_cast<float>(Tm);
+  const float df = math::exp_any(static_cast<float>(-r) * Tf);
+  const float Kf = static_cast<float>(c[0]);
+  const float wA = static_cast<float>(1.0 / A);
+  const float cT = Tm == 0.0 ? 0.0f : static_cast<float>(1.0 / (2.0 * Tm));
+  const float crho = df * (Tf * Kf);
+  const float rr = static_cast<float>(r);
+  auto forward = [&](int i) {
+    return static_cast<float>(c[4 + i]) * math::exp_any(static_cast<float>(r - c[4 + A + i]) * Tf);
+  };
+  // the constants that need no sum: g_ik (thread 8 i + k), and per asset ix0, cv, g0 and RAW's s, av, aT, ac.
+  // A deterministic asset (some v == 0) leaves no driver to recover: g = g0 = 0, the correlation columns NaN.
+  if (tid < kMaxAssets * kMaxAssets) {
+    const int i = tid >> 3, k = tid & 7;
+    float g = 0.0f;
+    if (i < A && k <= i && !anyv0)
+      g = static_cast<float>(c[4 + 2 * A + i] * Gd[i * kMaxAssets + k] / c[4 + 2 * A + k]);
+    gk[tid] = g;
+  }
+  if (tid < A) {
+    const int i = tid;
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double mu = r - d - 0.5 * v * v;
+    double gs = 0.0;
+    if (!anyv0)
+      for (int k = 0; k <= i; ++k) {
+        const double vk = c[4 + 2 * A + k];
+        const double muk = r - c[4 + A + k] - 0.5 * vk * vk;
+        gs = gs + Gd[i * kMaxAssets + k] * muk * Tm / vk;
+      }
+    float* f = fc + i * kBGreekFc;
+    f[0] = 1.0f;
+    f[1] = static_cast<float>(1.0 / c[4 + i]);
+    f[2] = v == 0.0 ? 0.0f : static_cast<float>(1.0 / v);
+    f[3] = v == 0.0 ? 0.0f : static_cast<float>(-mu * Tm / v - v * Tm);
+    f[4] = static_cast<float>(mu / 2.0);
+    f[5] = 0.0f;
+    f[6] = anyv0 ? 0.0f : static_cast<float>(-(v * gs));
+  }
+  __syncthreads();
+
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = P - chunk - kBPaths * static_cast<int64_t>(tid);
+    return static_cast<int>(left <= 0 ? 0 : (left >= kBPaths ? kBPaths : left));
+  };
+  auto simulate = [&](int64_t chunk, float(&x)[A][kBPaths]) {
+    PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+    basket_lane_paths<A, HW>(s, ca, x0, Lb, T, x);
+  };
+  // c_i = g0_i + sum_{k <= i} g_ik L_k in k order (every operation rounded)
+  auto corr = [&](int i, const float(&L)[A]) {
+    float ci = fc[i * kBGreekFc + 6];
+#pragma unroll
+    for (int k = 0; k < A; ++k)
+      if (k <= i) ci = ci + gk[i * kMaxAssets + k] * L[k];
+    return ci;
+  };
+  // terminal sums of one chunk in basket_price_kernel's order
+  auto add_terminal = [&](const float(&x)[A][kBPaths], int nvalid, double(&acc)[A]) {
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+      float p = 0.0f;
+#pragma unroll
+      for (int j = 0; j < kBPaths; ++j) p += j < nvalid ? x[i][j] : 0.0f;
+      acc[i] += static_cast<double>(p);
+    }
+  };
+  // a lane's partial of pass-1 sum q (0 tot, 1 sxl, 2 sxc) through the wave butterfly; finish_sums then adds
+  // waves 0..7 of the first nq sums (the others are 0) and reports them
+  auto wave_sums = [&](const double(&acc)[A], int q) {
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+      const double w = bwave_sum(acc[i]);
+      if (lane == 0) wsum[(wave * 3 + q) * kMaxAssets + i] = w;
+    }
+  };
+  auto finish_sums = [&](int nq) {
+    __syncthreads();
+    if (tid < 3 * kMaxAssets) {
+      const int q = tid >> 3, i = tid & 7;
+      if (i < A) {
+        double sum = 0.0;
+        if (q < nq)
+          for (int w = 0; w < kBWaves; ++w) sum += wsum[(w * 3 + q) * kMaxAssets + i];
+        tot[tid] = sum;
+        if (sums) sums[b * (3 * A) + q * A + i] = sum;
+      }
+    }
+    __syncthreads();
+  };
+  // One pass over the paths for the sums that come before the payoffs: TOT the terminal sums (the first pass
+  // over the paths: it simulates and, in the lds mode, parks), XLXC sxl_i = sum f64(x_i L_i) and
+  // sxc_i = sum f64(x_i c_i).  A <= 4 takes all three together; from A = 5 on the 3A accumulators do not fit
+  // beside the path loop, and TOT goes first, alone.
+  auto sum_pass = [&](auto tot_tag, auto xlxc_tag) {
+    constexpr bool TOT = decltype(tot_tag)::value, XLXC = decltype(xlxc_tag)::value;
+    double acc[3][A];
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+      for (int i = 0; i < A; ++i) acc[q][i] = 0.0;
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float x[A][kBPaths];
+        if constexpr (MODE == kBPriceLds && !TOT) {  // the lane's own values: no barrier needed
+#pragma unroll
+          for (int i = 0; i < A; ++i) {
+            const v4f q = park[(i * P4 + chunk) / kBPaths + tid];
+#pragma unroll
+            for (int j = 0; j < kBPaths; ++j) x[i][j] = q[j];
+          }
+        } else {
+          simulate(chunk, x);
+        }
+        if constexpr (TOT) add_terminal(x, nvalid, acc[0]);
+        if constexpr (XLXC) {
+#pragma unroll
+          for (int j = 0; j < kBPaths; ++j) {
+            if (j < nvalid) {
+              if constexpr (A > 4) asm volatile("" ::: "memory");  // the LDS constants are read per path, not kept
+              float L[A];
+#pragma unroll
+              for (int i = 0; i < A; ++i) L[i] = basket_greeks_log<HW>(x[i][j], x0[i]);
+#pragma unroll
+              for (int i = 0; i < A; ++i) {
+                acc[1][i] += static_cast<double>(x[i][j] * L[i]);
+                acc[2][i] += static_cast<double>(x[i][j] * corr(i, L));
+              }
+            }
+          }
+        }
+        if constexpr (MODE == kBPriceLds && TOT) {
+          // slot (chunk + 4 tid) / 4 of row i: chunk + 4 tid < P, so the slot ends at or before P4
+#pragma unroll
+          for (int i = 0; i < A; ++i)
+            park[(i * P4 + chunk) / kBPaths + tid] = v4f{x[i][0], x[i][1], x[i][2], x[i][3]};
+        }
+      }
+    }
+    if constexpr (TOT) wave_sums(acc[0], 0);
+    if constexpr (XLXC) {
+      wave_sums(acc[1], 1);
+      wave_sums(acc[2], 2);
+    }
+  };
+  constexpr bool kSplitSums = A > 4;
+  using yes = std::true_type;
+  using no = std::false_type;
+
+  if constexpr (MODE != kBPriceRaw) {
+    if constexpr (kSplitSums) {
+      sum_pass(yes{}, no{});
+      sum_pass(no{}, yes{});
+    } else {
+      sum_pass(yes{}, yes{});
+    }
+    finish_sums(3);
+    if (tid < A) {  // the constants that move with the sums
+      const int i = tid;
+      const double v = c[4 + 2 * A + i], rd = r - c[4 + A + i];
+      const double lbar = tot[kMaxAssets + i] / tot[i];
+      float* f = fc + i * kBGreekFc;
+      f[0] = forward(i) / static_cast<float>(tot[i] / static_cast<double>(P));
+      f[3] = v == 0.0 ? 0.0f : static_cast<float>(-lbar / v);
+      f[4] = Tm == 0.0 ? static_cast<float>(rd) : static_cast<float>(-lbar / (2.0 * Tm) + rd);
+      f[5] = static_cast<float>(-tot[2 * kMaxAssets + i] / tot[i]);
+    }
+    __syncthreads();
+  } else if constexpr (kSplitSums) {  // RAW from A = 5 on: the terminal sums in a pass of their own
+    sum_pass(yes{}, no{});
+    finish_sums(1);
+  }
+
+  // one path's terms of pass PASS (the table of the header), each cast to f64 and added with its square
+  double v[2 * TP];
+  auto payoffs = [&](auto tag, const float(&x)[A][kBPaths], int nvalid) {
+    constexpr int T0 = decltype(tag)::value * TP;
+#pragma unroll
+    for (int j = 0; j < kBPaths; ++j) {
+      if (j < nvalid) {
+        // from A = 5 on the LDS constants are read again for every path: held across the path loop (where the
+        // compiler hoists them to) they spill
+        if constexpr (A > 4) asm volatile("" ::: "memory");
+        float L[A], w[A], t[NT];
+        float bs = 0.0f;
+#pragma unroll
+        for (int i = 0; i < A; ++i) {
+          const float xs = x[i][j] * fc[i * kBGreekFc];
+          bs = bs + xs;
+          w[i] = (df * xs) * wA;
+          L[i] = basket_greeks_log<HW>(x[i][j], x0[i]);
+        }
+        const float bk = bs * wA;
+        const float dp = Kf - bk, dc = bk - Kf;
+        const bool ip = dp > 0.0f, ic = dc > 0.0f;
+        const float put = df * (ip ? dp : 0.0f), call = df * (ic ? dc : 0.0f);
+        float sT = 0.0f, sC = 0.0f;
+#pragma unroll
+        for (int i = 0; i < A; ++i) {
+          const float* f = fc + i * kBGreekFc;
+          const float wd = w[i] * f[1];
+          const float wv = w[i] * (L[i] * f[2] + f[3]);
+          sT = sT + w[i] * (L[i] * cT + f[4]);
+          sC = sC + w[i] * (corr(i, L) + f[5]);
+          t[i] = ip ? -wd : 0.0f;
+          t[A + i] = ic ? wd : 0.0f;
+          t[2 * A + i] = ip ? -wv : 0.0f;
+          t[3 * A + i] = ic ? wv : 0.0f;
+        }
+        t[4 * A] = ip ? -crho : 0.0f;
+        t[4 * A + 1] = ic ? crho : 0.0f;
+        t[4 * A + 2] = rr * put + (ip ? sT : 0.0f);
+        t[4 * A + 3] = rr * call - (ic ? sT : 0.0f);
+        t[4 * A + 4] = ip ? -sC : 0.0f;
+        t[4 * A + 5] = ic ? sC : 0.0f;
+        t[NG] = put;
+        t[NG + 1] = call;
+#pragma unroll
+        for (int k = 0; k < TP; ++k) {
+          if (T0 + k < NT) {
+            const double d = static_cast<double>(t[T0 + k]);
+            v[k] += d;
+            v[TP + k] += d * d;
+          }
+        }
+      }
+    }
+  };
+
+  const double n = static_cast<double>(P);
+  double* out = greeks + b * (2 * NG + 4);
+#pragma unroll 1
+  for (int pass = 0; pass < NP; ++pass) {
+#pragma unroll
+    for (int k = 0; k < 2 * TP; ++k) v[k] = 0.0;
+    double acc[A];  // RAW, A <= 4: the terminal sums ride along with the one payoff pass
+#pragma unroll
+    for (int i = 0; i < A; ++i) acc[i] = 0.0;
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float x[A][kBPaths];
+        if constexpr (MODE == kBPriceLds) {  // the lane's own values: no barrier needed
+#pragma unroll
+          for (int i = 0; i < A; ++i) {
+            const v4f q = park[(i * P4 + chunk) / kBPaths + tid];
+#pragma unroll
+            for (int j = 0; j < kBPaths; ++j) x[i][j] = q[j];
+          }
+        } else {
+          simulate(chunk, x);
+        }
+        if constexpr (MODE == kBPriceRaw && !kSplitSums) add_terminal(x, nvalid, acc);
+        basket_static_for(std::make_integer_sequence<int, NP>{}, [&](auto tag) {
+          if (NP == 1 || pass == decltype(tag)::value) payoffs(tag, x, nvalid);
+        });
+      }
+    }
+    if constexpr (MODE == kBPriceRaw && !kSplitSums) {
+      wave_sums(acc, 0);
+      finish_sums(1);  // sxl = sxc = 0
+    }
+    // the pass's sums: wave butterfly, waves 0..7, sum k totalled by thread k
+#pragma unroll
+    for (int k = 0; k < 2 * TP; ++k) {
+      const double w = bwave_sum(v[k]);
+      if (lane == 0) lds[wave * kBGreekRed + k] = w;
+    }
+    __syncthreads();
+    const int term = pass * TP + tid;
+    if (tid < TP && term < NT) {  // a term's mean and standard error
+      auto total = [&](int k) {
+        double t2 = 0.0;
+        for (int w = 0; w < kBWaves; ++w) t2 += lds[w * kBGreekRed + k];
+        return t2;
+      };
+      double m = total(tid) / n;
+      double se = 0.0;
+      if (P > 1) {
+        const double var = total(TP + tid) - n * m * m;
+        se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+      }
+      if (A > 1 && anyv0 && (term == 4 * A + 4 || term == 4 * A + 5)) m = se = __builtin_nan("");
+      if (term < NG) {
+        out[term] = m;
+        out[NG + term] = se;
+      } else {  // the prices: columns 2n, 2n + 1 and 2n + 2, 2n + 3
+        out[NG + term] = m;
+        out[NG + term + 2] = se;
+      }
+    }
+    if (NP > 1) __syncthreads();  // the partials are rewritten by the next pass
   }
 }
 
@@ -1102,6 +1506,53 @@ int32_t launch_basket_price(int A, const BasketArgs& a, int mode, size_t lds, do
   }
 }
 
+// basket_greeks_kernel's mode and dynamic LDS for a shape (host only, no HIP call): basket_price_mode's rule with
+// this kernel's scratch in the park bound; -1: not a call it takes.
+int basket_greeks_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
+  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
+  *lds = kBGreekScratch;
+  if (normalization == SMC_NORM_RAW) return kBPriceRaw;
+  if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
+  const size_t park = kBGreekScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
+  if (park > kBPriceParkBytes) return kBPriceReplay;
+  *lds = park;
+  return kBPriceLds;
+}
+
+template <int A, bool HW>
+int32_t launch_basket_greeks_k(const BasketArgs& a, int mode, size_t lds, double* greeks, double* sums,
+                               hipStream_t stream) {
+  auto kernel = mode == kBPriceRaw   ? basket_greeks_kernel<A, HW, kBPriceRaw>
+                : mode == kBPriceLds ? basket_greeks_kernel<A, HW, kBPriceLds>
+                                     : basket_greeks_kernel<A, HW, kBPriceReplay>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "basket_greeks_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, greeks, sums);
+  return check_launch("basket_greeks_kernel");
+}
+
+template <bool HW>
+int32_t launch_basket_greeks(int A, const BasketArgs& a, int mode, size_t lds, double* greeks, double* sums,
+                             hipStream_t stream) {
+  switch (A) {
+    case 1: return launch_basket_greeks_k<1, HW>(a, mode, lds, greeks, sums, stream);
+    case 2: return launch_basket_greeks_k<2, HW>(a, mode, lds, greeks, sums, stream);
+    case 3: return launch_basket_greeks_k<3, HW>(a, mode, lds, greeks, sums, stream);
+    case 4: return launch_basket_greeks_k<4, HW>(a, mode, lds, greeks, sums, stream);
+    case 5: return launch_basket_greeks_k<5, HW>(a, mode, lds, greeks, sums, stream);
+    case 6: return launch_basket_greeks_k<6, HW>(a, mode, lds, greeks, sums, stream);
+    case 7: return launch_basket_greeks_k<7, HW>(a, mode, lds, greeks, sums, stream);
+    case 8: return launch_basket_greeks_k<8, HW>(a, mode, lds, greeks, sums, stream);
+    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: n_assets must be in 1..8");
+  }
+}
+
 }  // namespace
 }  // namespace smc
 
@@ -1237,6 +1688,53 @@ const char* smc_basket_price_kernel(int32_t n_assets, int32_t timesteps, int64_t
     case kBPriceReplay: return "basket_price_kernel(replay)";
     default: return "unsupported";
   }
+}
+
+int32_t smc_basket_greeks(const double* contracts_dev, int64_t n_contracts, int32_t n_assets, int32_t timesteps,
+                          int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
+                          int32_t normalization, double* greeks_dev, double* sums_dev, void* stream) {
+  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: contracts_dev is NULL");
+  if (!greeks_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: greeks_dev is NULL");
+  if (n_assets < 1 || n_assets > kMaxAssets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: n_assets must be in 1..8");
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: bad normalization");
+  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_greeks: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
+  if (n_paths >= (int64_t{1} << 40)) return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_greeks: n_paths too large (>= 2^40)");
+  if (n_contracts == 0) return SMC_OK;
+  size_t lds = 0;
+  const int mode = basket_greeks_mode(n_assets, n_paths, math, normalization, &lds);
+  BasketArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.normalize = normalization != SMC_NORM_RAW;
+  return (math & SMC_MATH_HW)
+             ? launch_basket_greeks<true>(n_assets, a, mode, lds, greeks_dev, sums_dev, as_stream(stream))
+             : launch_basket_greeks<false>(n_assets, a, mode, lds, greeks_dev, sums_dev, as_stream(stream));
+}
+
+const char* smc_basket_greeks_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                     int32_t normalization) {
+  size_t lds = 0;
+  if (timesteps <= 0) return "unsupported";
+  switch (basket_greeks_mode(n_assets, n_paths, math, normalization, &lds)) {
+    case kBPriceRaw: return "basket_greeks_kernel(raw)";
+    case kBPriceLds: return "basket_greeks_kernel(lds)";
+    case kBPriceReplay: return "basket_greeks_kernel(replay)";
+    default: return "unsupported";
+  }
+}
+
+int32_t smc_basket_greeks_cols(int32_t n_assets) {
+  return n_assets < 1 || n_assets > kMaxAssets ? -1 : 8 * n_assets + 16;
 }
 
 #pragma GCC visibility pop
