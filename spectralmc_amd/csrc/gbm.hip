@@ -279,14 +279,19 @@ __device__ __forceinline__ void lane_paths(const EngineArgs& a, const Stepper<Re
         // the terminal row is read back by the CF phase (maybe another workgroup's): write-through
         const bool handoff = last && (STRAIGHT || a.targets != nullptr);
         if constexpr (STRAIGHT && !MASKED && sizeof(Real) == 4) {
-          // one buffer descriptor on the contract base; the row offset goes in soffset (SALU adds), so
-          // a row store costs no 64-bit VALU address add
+          // one buffer descriptor on the contract base and a 32-bit byte offset, so a row store costs one
+          // v_add_u32 and no 64-bit VALU address add.  The row offset must NOT ride in soffset: a
+          // buffer_store_dwordx4 with an SGPR soffset reads its data registers late on gfx950, and the compiler
+          // (which counts that form as free of the "VMEM store of more than 64 bits, then a VALU write of its
+          // data" hazard) let the next step's v_pk_mul_f32 overwrite x[0..1] in the very next slot: rows then held
+          // the following row's value in some lanes ("Parity of the single-asset engine").
+          // With the whole offset in voffset the compiler pads that hazard itself.
           typedef float v4f __attribute__((ext_vector_type(4)));
           const v4f v4 = {x[0], x[1], x[2], x[3]};
-          const uint32_t soff = static_cast<uint32_t>((chunk + (store_all ? static_cast<int64_t>(t) * pitch : 0)) *
-                                                      static_cast<int64_t>(sizeof(Real)));
-          if (handoff) __builtin_amdgcn_raw_buffer_store_b128(v4, contract_rsrc, lane_off, soff, 16 /* sc1 */);
-          else __builtin_amdgcn_raw_buffer_store_b128(v4, contract_rsrc, lane_off, soff, 0);
+          const uint32_t row_off = static_cast<uint32_t>((chunk + (store_all ? static_cast<int64_t>(t) * pitch : 0)) *
+                                                         static_cast<int64_t>(sizeof(Real)));
+          if (handoff) __builtin_amdgcn_raw_buffer_store_b128(v4, contract_rsrc, lane_off + row_off, 0, 16 /* sc1 */);
+          else __builtin_amdgcn_raw_buffer_store_b128(v4, contract_rsrc, lane_off + row_off, 0, 0);
         } else if constexpr (!MASKED) {
           V4 v4;
           v4.x = x[0];

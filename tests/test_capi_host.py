@@ -129,6 +129,28 @@ def test_host_sobol_bit_exact_with_reference(golden, seed, skip) -> None:
     assert eng.cursor == skip + 96
 
 
+@pytest.mark.parametrize("seed,skip", [(7, 0), (123, 4097), ((1 << 40) + 3, (1 << 29) + 5), (0, 0)])
+@pytest.mark.parametrize("dim", [1, 2, 7, 16, 19, 28, 40, 63, 64])
+def test_host_sobol_matches_scipy_at_every_dimension(dim, seed, skip) -> None:
+    """Every other bit-exact Sobol test is at dim = 6, but smc_sobol_create takes 1..64 dimensions and the basket
+    engine draws 3 A + 4 (up to 28): this pins the direction numbers of sobol_dirnums.h beyond their first six rows,
+    the seeding of the scramble at a seed beyond 32 bits and the Gray-code jump at a far index (where SciPy's
+    fast_forward walks every point: several seconds per dimension count)."""
+    import warnings
+
+    from scipy.stats.qmc import Sobol
+
+    ref = Sobol(d=dim, scramble=True, seed=seed)
+    if skip:
+        ref.fast_forward(skip)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # 257 is no power of two
+        want = ref.random(257)
+    eng = SobolEngine(dim, seed, skip)
+    np.testing.assert_array_equal(eng.random(257), want)
+    assert eng.cursor == skip + 257
+
+
 def test_sobol_tables_layout() -> None:
     eng = SobolEngine(6, 7, 0)
     shift, sv = eng.state()

@@ -20,6 +20,7 @@ import oracle as _oracle
 from spectralmc_amd import _lib
 from spectralmc_amd.gbm import BlackScholes
 from spectralmc_amd.models.numerical import Precision
+from tests.helpers import gbm_restate as gr
 from tests.helpers import ATOL_FLOAT64, RTOL_FLOAT64, assert_rows_equal, expect_success, poisoned
 from tests.test_gpu_price import ORD0, SEED, _contracts, _engine, _inputs, _price, _stderr
 
@@ -31,11 +32,7 @@ MEANS = (0, 1, 2, 3, 4, 5, 6, 7, 16, 18, 19)
 NAMES = ("asian put", "asian call", "knock-out put", "knock-out call", "lookback put", "lookback call", "put", "call")
 
 
-def _barriers(c: np.ndarray) -> np.ndarray:
-    """[B, 2] (lower, upper): L = X0 exp(-v sqrt(T)), U = max(X0, F) exp(v sqrt(T))."""
-    X0, Tm, v = c[:, 0], c[:, 2], c[:, 5]
-    F = X0 * np.exp((c[:, 3] - c[:, 4]) * Tm)
-    return np.stack([X0 * np.exp(-v * np.sqrt(Tm)), np.maximum(X0, F) * np.exp(v * np.sqrt(Tm))], axis=1)
+_barriers = gr.barriers
 
 
 def _paths(c: np.ndarray, T: int, P: int, scheme: int, norm: int, dtype: int = 0, ordinal0: int = 0,
@@ -57,79 +54,14 @@ def _got(B: int, T: int, P: int, scheme: int, norm: int, dtype: int = 0, with_ba
     return out
 
 
-def _time_grid(c: np.ndarray, T: int) -> np.ndarray:
-    """[B, T] f64: linspace(dt, T, T), last point exact."""
-    return np.stack([np.linspace(Tm / T, Tm, T, dtype=np.float64) for Tm in c[:, 2]])
-
-
-def _block(xs: np.ndarray, K: np.ndarray, df: np.ndarray, lower: np.ndarray, upper: np.ndarray) -> dict[str, np.ndarray]:
-    """The 20 columns (and m^2 / var of the 8 payoffs, [B, 8]) from the scaled rows xs [B, T, P] and K, df, the
-    barriers [B], all in the sim dtype: the per-path state row by row in that dtype, the sums in float64."""
-    B, T, P = xs.shape
-    real = xs.dtype.type
-    zero = real(0)
-    a = np.zeros((B, P), dtype=xs.dtype)
-    mx = np.full((B, P), -np.inf, dtype=xs.dtype)
-    mn = np.full((B, P), np.inf, dtype=xs.dtype)
-    ko = np.zeros((B, P), dtype=bool)
-    for t in range(T):
-        row = xs[:, t, :]
-        a = a + row
-        mx = np.maximum(mx, row)
-        mn = np.minimum(mn, row)
-        ko |= (row <= lower[:, None]) | (row >= upper[:, None])
-    avg = a / real(T)
-    last = xs[:, T - 1, :]
-    assert avg.dtype == xs.dtype and K.dtype == xs.dtype and df.dtype == xs.dtype and lower.dtype == xs.dtype
-
-    def pay(diff: np.ndarray) -> np.ndarray:
-        v = df[:, None] * np.maximum(diff, zero)
-        assert v.dtype == xs.dtype
-        return v.astype(np.float64)
-
-    Kc = K[:, None]
-    put, call = pay(Kc - last), pay(last - Kc)
-    pays = [pay(Kc - avg), pay(avg - Kc), np.where(ko, 0.0, put), np.where(ko, 0.0, call), pay(Kc - mn), pay(mx - Kc),
-            put, call]
-    s1 = np.stack([v.sum(axis=1) for v in pays], axis=1)
-    s2 = np.stack([(v * v).sum(axis=1) for v in pays], axis=1)
-    cols = np.empty((B, COLS))
-    cols[:, :8] = s1 / P
-    cols[:, 8:16] = _stderr(s1, s2, P)
-    cols[:, 16] = avg.astype(np.float64).sum(axis=1) / P
-    cols[:, 17] = ko.sum(axis=1) / P
-    cols[:, 18] = mx.astype(np.float64).sum(axis=1) / P
-    cols[:, 19] = mn.astype(np.float64).sum(axis=1) / P
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rho = np.square(s1 / P) / np.maximum(s2 / P - np.square(s1 / P), 1e-300)
-    return {"cols": cols, "m2_over_var": rho}
+_time_grid = gr.time_grid
+_block = gr.path_block
 
 
 @functools.lru_cache(maxsize=None)
 def _restated_f32(B: int, T: int, P: int, scheme: int, norm: int) -> dict[str, np.ndarray]:
-    _oracle.build()
     c = _contracts(B)
-    paths, _, rs = _oracle.kernel_paths(c, T, P, SEED, ORD0, scheme, want_paths=True)
-    exp2 = _oracle.oracle.lib().oracle_exp2
-    f32 = np.float32
-
-    def exp_any(x: np.ndarray) -> np.ndarray:
-        flat = [exp2(float(f32(v) * f32(1.44269502))) for v in x.ravel()]
-        return np.array(flat, dtype=f32).reshape(x.shape)
-
-    Tm = c[:, 2].astype(f32)
-    df = exp_any((-c[:, 3]).astype(f32) * Tm)
-    K = c[:, 1].astype(f32)
-    if norm:
-        F = c[:, 0].astype(f32)[:, None] * exp_any((c[:, 3] - c[:, 4]).astype(f32)[:, None] * _time_grid(c, T).astype(f32))
-        s = F / (rs / P).astype(f32)
-        assert s.dtype == f32 and s.shape == (B, T)
-        xs = paths * s[:, :, None]
-    else:
-        xs = paths
-    assert xs.dtype == f32
-    bars = _barriers(c).astype(f32)
-    return _block(xs, K, df, bars[:, 0], bars[:, 1])
+    return gr.path_price_f32(_oracle, c, _barriers(c), T, P, SEED, ORD0, scheme, norm)
 
 
 def _restated_f64(B: int, T: int, P: int, scheme: int, norm: int) -> dict[str, np.ndarray]:

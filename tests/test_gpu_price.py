@@ -20,6 +20,7 @@ import oracle as _oracle
 from spectralmc_amd import _lib
 from spectralmc_amd.gbm import BlackScholes
 from spectralmc_amd.models.numerical import Precision
+from tests.helpers import gbm_restate as gr
 from tests.helpers import (
     ATOL_FLOAT64,
     RTOL_FLOAT64,
@@ -37,18 +38,7 @@ SEED = 7
 COLS = _lib.PRICE_COLS
 
 
-@functools.lru_cache(maxsize=None)
-def _contracts(n: int) -> np.ndarray:
-    rng = np.random.default_rng(2026)
-    rows = []
-    for _ in range(n):
-        x0 = rng.uniform(50, 150)
-        k = x0 * rng.uniform(0.8, 1.25)
-        rows.append([x0, k, rng.uniform(0.25, 2), rng.uniform(-0.02, 0.08), rng.uniform(0, 0.04),
-                     rng.uniform(0.1, 0.6)])
-    out = np.array(rows, dtype=np.float64)
-    out.setflags(write=False)
-    return out
+_contracts = gr.contracts
 
 
 def _price(c: np.ndarray, T: int, P: int, scheme: int, norm: int, dtype: int = 0, ordinal0: int = 0,
@@ -61,50 +51,13 @@ def _price(c: np.ndarray, T: int, P: int, scheme: int, norm: int, dtype: int = 0
     return out.cpu().numpy()
 
 
-def _stderr(s1: np.ndarray, s2: np.ndarray, P: int) -> np.ndarray:
-    if P == 1:
-        return np.zeros_like(s1)
-    m = s1 / P
-    return np.sqrt(np.maximum(s2 - P * m * m, 0.0) / (P - 1) / P)
-
-
-def _block(xs: np.ndarray, K: np.ndarray, F: np.ndarray, df: np.ndarray, tsum: np.ndarray) -> dict[str, np.ndarray]:
-    """The 8 columns (and m^2 / var of put and call, [B,2]) from xs [B,P], K, F, df [B] in the sim dtype."""
-    P = xs.shape[1]
-    zero = xs.dtype.type(0)
-    put = (df[:, None] * np.maximum(K[:, None] - xs, zero)).astype(np.float64)
-    call = (df[:, None] * np.maximum(xs - K[:, None], zero)).astype(np.float64)
-    sp, sc = put.sum(axis=1), call.sum(axis=1)
-    sp2, sc2 = (put * put).sum(axis=1), (call * call).sum(axis=1)
-    cols = np.stack([sp / P, sc / P, xs.astype(np.float64).sum(axis=1) / P, _stderr(sp, sp2, P), _stderr(sc, sc2, P),
-                     (df * np.maximum(K - F, zero)).astype(np.float64),
-                     (df * np.maximum(F - K, zero)).astype(np.float64), tsum], axis=1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = [np.square(s / P) / np.maximum(s2 / P - np.square(s / P), 1e-300) for s, s2 in ((sp, sp2), (sc, sc2))]
-    return {"cols": cols, "m2_over_var": np.stack(ratio, axis=1), "F": F.astype(np.float64),
-            "df": df.astype(np.float64)}
+_stderr = gr.stderr
+_block = gr.price_block
 
 
 @functools.lru_cache(maxsize=None)
 def _restated_f32(B: int, T: int, P: int, scheme: int, norm: int, ordinal0: int) -> dict[str, np.ndarray]:
-    _oracle.build()
-    c = _contracts(B)
-    _, term, rs = _oracle.kernel_paths(c, T, P, SEED, ordinal0, scheme)
-    exp2 = _oracle.oracle.lib().oracle_exp2
-    f32 = np.float32
-
-    def exp_any(x: np.ndarray) -> np.ndarray:
-        return np.array([exp2(float(f32(v) * f32(1.44269502))) for v in x], dtype=f32)
-
-    Tm = c[:, 2].astype(f32)
-    F = c[:, 0].astype(f32) * exp_any((c[:, 3] - c[:, 4]).astype(f32) * Tm)
-    df = exp_any((-c[:, 3]).astype(f32) * Tm)
-    K = c[:, 1].astype(f32)
-    tsum = rs[:, -1].copy()
-    s = F / (tsum / P).astype(f32) if norm else np.ones(B, dtype=f32)
-    xs = term * s[:, None]
-    assert xs.dtype == f32 and F.dtype == f32 and df.dtype == f32
-    return _block(xs, K, F, df, tsum)
+    return gr.price_f32(_oracle, _contracts(B), T, P, SEED, ordinal0, scheme, norm)
 
 
 def _restated_f64(B: int, T: int, P: int, scheme: int, norm: int, ordinal0: int) -> dict[str, np.ndarray]:
