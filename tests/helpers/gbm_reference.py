@@ -103,6 +103,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from tests.helpers.basket_reference import HW, PORTABLE, MathEps, complex_share_used, compose, share_used
+from tests.helpers.math_inputs import sincos_u32_angle_units
 
 __all__ = ["HW", "PORTABLE", "MathEps", "complex_share_used", "compose", "share_used"]
 
@@ -182,14 +183,20 @@ def stream_words(oracle, B: int, T: int, P: int, seed: int, ordinal0: int, *, sp
 
 
 def normals(words: np.ndarray, T: int, P: int, *, exchange: bool = False, tail_stride: bool = False,
-            complement: bool = True) -> tuple[np.ndarray, np.ndarray]:
+            complement: bool = True, f64: bool = False) -> tuple[np.ndarray, np.ndarray]:
     """(z, radius) [B, T, P] float64 of stream_words(...).  Wrong readings: exchange (the sine to step t, the cosine to
-    t + 1), tail_stride (pair k of the odd tail to paths k and k + 2), complement = False (u1 = (a >> 9) 2^-23)."""
+    t + 1), tail_stride (pair k of the odd tail to paths k and k + 2), complement = False (u1 = (a >> 9) 2^-23).
+    f64: the uniforms of the float64 engine, in the same draw order: u1 = (a + 1/2) 2^-32 and the angle of all 32
+    bits of b (math_inputs.sincos_u32_angle_units 2^-32 revolutions)."""
     B, G, n = words.shape
     assert n == 4 * T and words.dtype == np.uint32
-    m = (words[..., 0::2] >> np.uint32(9)).astype(np.float64) * 2.0 ** -23
-    u1 = 1.0 - m if complement else m
-    angle = 2.0 * np.pi * ((words[..., 1::2] >> np.uint32(9)).astype(np.float64) * 2.0 ** -23)
+    if f64:
+        u1 = (words[..., 0::2].astype(np.float64) + 0.5) * 2.0 ** -32
+        angle = 2.0 * np.pi * (sincos_u32_angle_units(words[..., 1::2]).astype(np.float64) * 2.0 ** -32)
+    else:
+        m = (words[..., 0::2] >> np.uint32(9)).astype(np.float64) * 2.0 ** -23
+        u1 = 1.0 - m if complement else m
+        angle = 2.0 * np.pi * ((words[..., 1::2] >> np.uint32(9)).astype(np.float64) * 2.0 ** -23)
     with np.errstate(divide="ignore", invalid="ignore"):
         radius = np.sqrt(np.abs(-2.0 * np.log(u1)))  # abs: -2 ln 1 is -0.0; [B, G, 2 T]
         first, second = radius * np.cos(angle), radius * np.sin(angle)

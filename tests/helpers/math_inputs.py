@@ -16,6 +16,9 @@ LOG_POS_MAX_ABS = 5.4e-7
 RADIUS_MAX_ABS = 3.5e-7  # |sqrtf(-2 log_pos(u1)) - sqrt(-2 ln u1)| over all 2^23 u1
 SINCOS_MAX_ABS = 8.6e-8  # sincos2pi_u24 over all 2^24 angles
 EXP2_MAX_REL = 7.7e-8  # exp2_any on the 2^-16 grid over [-126, 127]
+# log_pos over q_all(): every f32 in [2^-8, 2^8), the domain greeks_log takes it on (measured 1.2717e-7 and 4.8878e-8)
+LOG_POS_Q_MAX_REL = 1.28e-7  # relative, q outside [1 / sqrt 2, sqrt 2)
+LOG_POS_Q_MAX_ABS = 4.9e-8  # absolute, q inside it
 # SMC_MATH_HW: maxima measured on an MI355X over the whole domain of each factor (the hardware is deterministic per
 # input, so these are the true maxima of this build); the tests assert twice each (the *_BOUND names), which leaves
 # room for a compiler that lowers a builtin through another instruction form and nothing else.
@@ -25,12 +28,16 @@ HW_COS_MAX_ABS = 1.2527e-07
 HW_EXP2_MAX_REL = 8.1403e-08  # v_exp_f32 on the 2^-16 grid over [-126, 127]
 HW_LOG_MAX_REL = 1.6095e-07  # hw_log over the u1 <= 1/2
 HW_LOG_MAX_ABS = 7.2019e-08  # hw_log over the u1 > 1/2 (ln u1 -> 0)
+HW_LOG_Q_MAX_REL = 1.6326e-07  # hw_log over q_all() outside [1 / sqrt 2, sqrt 2) (at q in [2^-5, 2^-4))
+HW_LOG_Q_MAX_ABS = 3.2230e-08  # hw_log over q_all() inside it (at q in [1 / sqrt 2, 1))
 HW_RADIUS_BOUND = 2 * HW_RADIUS_MAX_ABS
 HW_SIN_BOUND = 2 * HW_SIN_MAX_ABS
 HW_COS_BOUND = 2 * HW_COS_MAX_ABS
 HW_EXP2_BOUND = 2 * HW_EXP2_MAX_REL
 HW_LOG_REL_BOUND = 2 * HW_LOG_MAX_REL
 HW_LOG_ABS_BOUND = 2 * HW_LOG_MAX_ABS
+HW_LOG_Q_REL_BOUND = 2 * HW_LOG_Q_MAX_REL
+HW_LOG_Q_ABS_BOUND = 2 * HW_LOG_Q_MAX_ABS
 
 # ---- portable f32 ------------------------------------------------------------------------------------------------
 
@@ -47,6 +54,32 @@ def a_of_u1(u1: float) -> int:
     m = int(round((2.0 - u1) * 2.0**23)) - (1 << 23)
     assert 0 <= m < 1 << 23 and 2.0 - (1.0 + m * 2.0**-23) == u1
     return m << 9
+
+
+Q_EXPONENTS = tuple(range(-8, 8))
+
+
+def q_of_exponent(e: int) -> np.ndarray:
+    """The 2^23 f32 values in [2^e, 2^(e + 1)): every mantissa at one binary exponent."""
+    assert -126 <= e <= 127
+    return (np.uint32((e + 127) << 23) | np.arange(1 << 23, dtype=np.uint32)).view(np.float32)
+
+
+def q_all():
+    """The domain greeks_log takes the logs on, q = x_T / X0 in [2^-8, 2^8) (v sqrt(T) up to about 1.1 at five standard
+    deviations): every f32 in it, one exponent at a time."""
+    return (q_of_exponent(e) for e in Q_EXPONENTS)
+
+
+def log_q_errors(q: np.ndarray, got: np.ndarray) -> tuple[float, float]:
+    """(max relative error of got against numpy's f64 log over the q outside [1 / sqrt 2, sqrt 2), max absolute error
+    over those inside it); 0 where a side is empty."""
+    q64 = q.astype(np.float64)
+    want = np.log(q64)
+    err = np.abs(got.astype(np.float64) - want)
+    inside = (q64 >= np.sqrt(0.5)) & (q64 < np.sqrt(2.0))
+    rel = float((err[~inside] / np.abs(want[~inside])).max()) if not inside.all() else 0.0
+    return rel, float(err[inside].max()) if inside.any() else 0.0
 
 
 EXP2_EDGES = np.array(

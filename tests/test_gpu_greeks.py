@@ -1,6 +1,6 @@
 """Batched pathwise Greeks (smc_gbm_greeks / BlackScholes.greeks_batch): the [B][26] block of greeks_kernel
-against the CPU restatement of the table in include/spectralmc_hip.h, bit for bit where the kernel promises it
-(the raw terminal sum, the price call's columns, the modes, run to run and under a split of the batch), within
+against the CPU restatement of the table in include/spectralmc_hip.h (tests/helpers/greeks_restate.py), bit for
+bit where the kernel promises it (the raw terminal sum, the price call's columns, the modes, run to run and under a split of the batch), within
 stated rounding bounds elsewhere, and against the Black-Scholes closed forms within the Monte-Carlo error.
 
 The f32 expectation follows the header's formulas operation by operation in numpy float32 on the oracle's
@@ -31,6 +31,10 @@ from tests.helpers import (
     make_simulation_params,
     poisoned,
 )
+from tests.helpers.greeks_restate import check_stderr as _check_stderr
+from tests.helpers.greeks_restate import log_pos_f32 as _log_pos_f32
+from tests.helpers.greeks_restate import summary as _summary
+from tests.helpers.greeks_restate import terms as _terms
 
 pytestmark = pytest.mark.gpu
 
@@ -80,112 +84,6 @@ def _price(c: np.ndarray, T: int, P: int, scheme: int, norm: int, dtype: int = 0
 
 def _name(T: int, P: int, scheme: int, norm: int, dtype: int = 0) -> str:
     return _lib.lib().smc_gbm_greeks_kernel(T, P, scheme, norm, dtype).decode()
-
-
-# --------------------------------------------------------------------------- the restatement
-def _log_pos_f32(q: np.ndarray) -> np.ndarray:
-    fn = _oracle.oracle.lib().oracle_log_pos
-    return np.array([fn(v) for v in q.ravel().tolist()], dtype=np.float32).reshape(q.shape)
-
-
-def _exp_any_f32(x: np.ndarray) -> np.ndarray:
-    exp2 = _oracle.oracle.lib().oracle_exp2
-    f32 = np.float32
-    return np.array([exp2(float(f32(v) * f32(1.44269502))) for v in x], dtype=f32)
-
-
-def _terms(c: np.ndarray, term: np.ndarray, norm: int, sumx: np.ndarray, sumxl: np.ndarray | None,
-           L: np.ndarray) -> dict[str, np.ndarray]:
-    """The header's table on terminal values term [B,P] and their logs L [B,P] (both in the sim dtype): the ten
-    per-path terms [10,B,P] in the sim dtype.  Every constant is taken in float64 from the contract row (and, under
-    NORMALIZE, from sumx and sumxl) and rounded to the sim dtype; every per-path operation is rounded to it."""
-    real = term.dtype.type
-    P = term.shape[1]
-    X0, K64, Tm, r, d, v = (c[:, i] for i in range(6))
-    Tr = Tm.astype(real)
-    if real is np.float32:
-        F = X0.astype(real) * _exp_any_f32((r - d).astype(real) * Tr)
-        df = _exp_any_f32((-r).astype(real) * Tr)
-    else:
-        F = X0 * np.exp((r - d) * Tm)
-        df = np.exp(-r * Tm)
-    K = K64.astype(real)
-    s = F / (sumx / P).astype(real) if norm else np.ones(len(c), dtype=real)
-    mu = r - d - 0.5 * v * v
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ix0 = (1.0 / X0).astype(real)
-        cv = np.where(v == 0, 0.0, 1.0 / v).astype(real)
-        cT = np.where(Tm == 0, 0.0, 1.0 / (2.0 * Tm)).astype(real)
-        crho = df * (Tr * K)
-        rr = r.astype(real)
-        if norm:
-            lbar = sumxl / sumx
-            av = np.where(v == 0, 0.0, -lbar / v).astype(real)
-            aT = np.where(Tm == 0, r - d, -lbar / (2.0 * Tm) + (r - d)).astype(real)
-        else:
-            av = np.where(v == 0, 0.0, -mu * Tm / v - v * Tm).astype(real)
-            aT = (mu / 2.0).astype(real)
-    col = lambda a: a[:, None]  # noqa: E731
-    zero = real(0)
-    xs = term * col(s)
-    dp, dc = col(K) - xs, xs - col(K)
-    ip, ic = dp > zero, dc > zero
-    put = col(df) * np.where(ip, dp, zero)
-    call = col(df) * np.where(ic, dc, zero)
-    w = col(df) * xs
-    hv = L * col(cv) + col(av)
-    hT = L * col(cT) + col(aT)
-    wd, wv, wt = w * col(ix0), w * hv, w * hT
-    crho_b = np.broadcast_to(col(crho), xs.shape)
-    t = np.stack([np.where(ip, -wd, zero), np.where(ic, wd, zero),
-                  np.where(ip, -wv, zero), np.where(ic, wv, zero),
-                  np.where(ip, -crho_b, zero), np.where(ic, crho_b, zero),
-                  col(rr) * put + np.where(ip, wt, zero), col(rr) * call - np.where(ic, wt, zero),
-                  put, call])
-    assert t.dtype == term.dtype and xs.dtype == term.dtype and hv.dtype == term.dtype
-    return {"t": t, "xs": xs, "K": K, "crho": crho.astype(np.float64), "df": df.astype(np.float64),
-            "F": F.astype(np.float64)}
-
-
-def _summary(t: np.ndarray, c: np.ndarray) -> dict[str, np.ndarray]:
-    """From the terms [10,B,P]: the 24 columns 0..23 (float64 sums) and, per mean column 0..9 and price column,
-    the sum-order bound P 2^-52 sum|term| / P and the ratio (mean|term|)^2 / var of the standard-error bound."""
-    P = t.shape[2]
-    t64 = t.astype(np.float64)
-    s1, s2, sa = t64.sum(axis=2), (t64 * t64).sum(axis=2), np.abs(t64).sum(axis=2)   # [10,B]
-    m = s1 / P
-    D = np.maximum(s2 - P * m * m, 0.0)
-    se = np.sqrt(D / (P - 1) / P) if P > 1 else np.zeros_like(m)
-    bound = P * 2.0 ** -52 * sa / P
-    den = c[:, 5] * c[:, 2] * c[:, 0] * c[:, 0]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        g = lambda a: np.where(c[:, 5] * c[:, 2] == 0, 0.0, a / den)  # noqa: E731
-        cols = np.stack([*m[:8], g(m[2]), g(m[3]), *se[:8], g(se[2]), g(se[3]), m[8], m[9], se[8], se[9]], axis=1)
-        gb = np.stack([*bound[:8], g(bound[2]) + 2.0 ** -52 * np.abs(g(m[2])), g(bound[3]) + 2.0 ** -52 * np.abs(g(m[3]))])
-        rho = np.square(sa / P) / (D / P)   # inf where every term is the same: see _check_stderr
-    # the term order of the 12 mean-and-error pairs of the block: columns (i, 10 + i) for i < 10, then (20, 22), (21, 23)
-    return {"cols": cols, "bound": gb, "dD": P * 2.0 ** -52 * (s2 + 2 * sa * sa / P), "D": D, "rho": rho,
-            "price_bound": bound[8:10]}
-
-
-def _check_stderr(got: np.ndarray, want: np.ndarray, summ: dict[str, np.ndarray], term: int, P: int, what: str,
-                  scale: np.ndarray | None = None) -> None:
-    """test_gpu_price's derivation for D = sum v^2 - P m^2 with e = P 2^-52: sum v^2 moves by e sum v^2 and P m^2
-    by 2 e (sum |v|)^2 / P, so D by e (1 + 3 rho) D with rho = (mean |v|)^2 / var (m^2 / var for a term of one
-    sign), halved by the square root: within 8 e max(1, rho / 2) relative.  Where D is not above four times that
-    absolute movement dD (every path gives the same term, so D is rounding noise), only
-    |sqrt(a) - sqrt(b)| <= sqrt(|a - b|) holds: within sqrt(dD / ((P - 1) P))."""
-    e = P * 2.0 ** -52
-    k = 1.0 if scale is None else scale
-    D, dD, rho = summ["D"][term], summ["dD"][term], summ["rho"][term]
-    flat = D <= 4 * dD
-    with np.errstate(invalid="ignore"):
-        tol = np.where(flat, np.sqrt(dD / max(P - 1, 1) / P) * k, 8 * e * np.maximum(1.0, rho / 2) * np.abs(want))
-    err = np.abs(got - want)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        share = np.where(err == 0, 0.0, err / tol)
-    print(f"{what} stderr: max share of its bound {share.max():.3f} ({int(flat.sum())} flat)")
-    assert np.all(err <= tol), (what, int(np.argmax(share)))
 
 
 @functools.lru_cache(maxsize=None)

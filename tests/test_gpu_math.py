@@ -73,6 +73,13 @@ def test_log_pos_bit_exact_over_every_uniform(oracle) -> None:
     assert_rows_equal(math_eval("LOG_POS", u1, F32), oracle.log_pos_n(u1), "LOG_POS")
 
 
+@pytest.mark.parametrize("e", mi.Q_EXPONENTS)
+def test_log_pos_bit_exact_over_the_greeks_domain(oracle, e) -> None:
+    """q = x_T / X0 on both sides of 1 (greeks_log): every f32 in [2^-8, 2^8), one exponent per case."""
+    q = mi.q_of_exponent(e)
+    assert_rows_equal(math_eval("LOG_POS", q, F32), oracle.log_pos_n(q), "LOG_POS")
+
+
 def test_sincos2pi_u24_bit_exact_over_every_angle(oracle) -> None:
     j = np.arange(1 << 24, dtype=np.uint32)
     assert_rows_equal(math_eval("SINCOS_U24", j, F32, out_width=2), oracle.sincos2pi_u24_n(j), "SINCOS_U24")
@@ -301,3 +308,18 @@ def test_hw_exp2_and_log_maxima() -> None:
     assert rel.max() <= mi.HW_EXP2_BOUND
     assert lrel.max() <= mi.HW_LOG_REL_BOUND
     assert labs.max() <= mi.HW_LOG_ABS_BOUND
+
+
+@pytest.mark.parametrize("e", mi.Q_EXPONENTS)
+def test_hw_log_over_the_greeks_domain(e) -> None:
+    """hw_log where greeks_log<.., true> takes it: every f32 q in [2^e, 2^(e + 1)) against numpy's f64 log, relative
+    outside [1 / sqrt 2, sqrt 2) and absolute inside; twice the maxima measured over all 16 exponents."""
+    q = mi.q_of_exponent(e)
+    lg = math_eval("HW_LOG", q, F32)
+    rel, ab = mi.log_q_errors(q, lg)
+    print(f"HW_LOG on [2^{e}, 2^{e + 1}): max relative {rel:.4e}, max absolute {ab:.4e}")
+    assert not np.isnan(lg).any()
+    if e == 0:
+        assert lg[0] == 0.0
+    assert rel <= mi.HW_LOG_Q_REL_BOUND
+    assert ab <= mi.HW_LOG_Q_ABS_BOUND

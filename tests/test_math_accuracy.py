@@ -41,6 +41,22 @@ def test_log_pos_over_every_uniform(oracle) -> None:
     assert np.all(got[1:] < 0.0)
 
 
+@pytest.mark.parametrize("e", mi.Q_EXPONENTS)
+def test_log_pos_over_the_greeks_domain(oracle, e) -> None:
+    """log_pos where greeks_log takes it: q = x_T / X0 on both sides of 1, every mantissa of one binary exponent per
+    case, against numpy's f64 log.  Relative outside [1 / sqrt 2, sqrt 2), absolute inside (what hv and hT feel)."""
+    q = mi.q_of_exponent(e)
+    assert q.size == 1 << 23 and q[0] == F32(2.0**e) and np.all(np.diff(q) > 0) and q[-1] < F32(2.0 ** (e + 1))
+    got = oracle.log_pos_n(q)
+    rel, ab = mi.log_q_errors(q, got)
+    print(f"log_pos on [2^{e}, 2^{e + 1}): max relative {rel:.4e}, max absolute {ab:.4e}")
+    assert rel <= mi.LOG_POS_Q_MAX_REL
+    assert ab <= mi.LOG_POS_Q_MAX_ABS
+    assert np.all(np.diff(got) >= 0)  # monotone over the exponent
+    if e == 0:
+        assert got[0] == 0.0 and not np.signbit(got[0])
+
+
 def test_sincos2pi_u24_over_every_angle(oracle) -> None:
     j = np.arange(1 << 24, dtype=np.uint32)
     sc = oracle.sincos2pi_u24_n(j)
