@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 20  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks */
+#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -458,7 +458,8 @@ const char* smc_gbm_price_paths_kernel(int32_t timesteps, int64_t n_paths, int32
  * Contract values are not validated on the device, as in the engine: an indefinite correlation matrix
  * (rho <= -1 / (A - 1)) gives NaN, and rho = 1 is only meaningful for A <= 2 (from A = 3 on the
  * Banachiewicz factorisation divides 0 by 0).  B below the CU count leaves CUs idle (a contract is not split
- * over workgroups).  Equal weights and equicorrelation only; no path-dependent basket payoffs. */
+ * over workgroups).  Equal weights and equicorrelation only (caller weights and a general correlation matrix:
+ * smc_basket_price_general, below); no path-dependent basket payoffs. */
 #define SMC_BASKET_PRICE_COLS 18
 int32_t smc_basket_price(const double* contracts_dev /*[B][3A+4]*/, int64_t n_contracts, int32_t n_assets,
                          int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
@@ -594,8 +595,8 @@ const char* smc_gbm_greeks_kernel(int32_t timesteps, int64_t n_paths, int32_t sc
  * normalization.  SMC_ERR_INVALID_SHAPE: n_contracts < 0 or >= 2^31, timesteps <= 0, n_paths <= 0 or >= 2^40.
  * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  B below the CU count leaves CUs idle.
  * Out of scope: Greeks of the best-of / worst-of payoffs; gammas and cross-gammas (no diagonal lognormal identity
- * holds for a basket); caller weights and general correlation matrices; a float64 basket engine; likelihood-ratio
- * estimators. */
+ * holds for a basket); Greeks of the weighted, general-correlation basket (smc_basket_price_general prices it) and
+ * sensitivities to single correlation entries; a float64 basket engine; likelihood-ratio estimators. */
 int32_t smc_basket_greeks(const double* contracts_dev /*[B][3A+4]*/, int64_t n_contracts, int32_t n_assets,
                           int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
                           int64_t ordinal0, int32_t math, int32_t normalization,
@@ -606,6 +607,55 @@ const char* smc_basket_greeks_kernel(int32_t n_assets, int32_t timesteps, int64_
                                      int32_t normalization);
 /* Doubles per contract of greeks_dev: 8 n_assets + 16; -1 for n_assets outside 1..8. */
 int32_t smc_basket_greeks_cols(int32_t n_assets);
+
+/* ---- weighted, general-correlation basket pricing (ABI 21) ----------------------
+ * smc_basket_price with the two things a real index or spread has of its own: weights and a full correlation
+ * matrix, per contract or shared.  Taken unchanged from smc_basket_price: the contract rows ([B][3A+4]: K, T, r,
+ * rho, X0[A], d[A], v[A]), the streams (contract b uses ordinal (*ordinal_dev or 0) + ordinal0 + b), the 512-lane
+ * workgroup per contract, the chunking and the handling of any n_paths >= 1, the raw / lds / replay modes, the
+ * fixed sum orders, the 18 columns of prices_dev (SMC_BASKET_PRICE_COLS), terminal_sum_dev and math (0 or
+ * SMC_MATH_HW, optionally | SMC_PRICE_REPLAY).  New, for contract b:
+ *   weights      w_i = f32(weights_dev[b * weights_stride + i]); f32(1.0 / A) when weights_dev is NULL.  Stride 0
+ *                shares row 0 with every contract.  Any finite value is taken, negatives included (spread and
+ *                exchange options); the weights are not normalised.
+ *   correlation  for k < i, C_ik = corr_dev[b * corr_stride + i (i - 1) / 2 + k]: the strict lower triangle row by
+ *                row, (1,0), (2,0), (2,1), (3,0), ...  When corr_dev is NULL, C_ik is the row's rho; otherwise the
+ *                rho column is ignored.  C_ii = 1.  Stride 0 shares row 0.  At A = 1 nothing is read.
+ *   factor       the engine's Banachiewicz statements with rho replaced by C_ik, in f64, by one thread, in LDS:
+ *                for i, for k <= i: s = (i == k ? 1 : C_ik); for m < k: s = s - L_im L_km;
+ *                L_ik = i == k ? sqrt(s > 0 ? s : 0) : s / L_kk.  Step coefficients as smc_basket_price's.
+ * Per path, in f32, every operation rounded (no fused multiply-add), with s_i, tot_i, F_i, df and K exactly
+ * smc_basket_price's:
+ *   xs_i = x_i s_i    t_i = w_i xs_i    bk = ((0 + t_0) + t_1) + ...    mx = max_i xs_i    mn = min_i xs_i
+ * (mx and mn are over the unweighted xs_i).  Payoffs, sums, standard errors and the exercise share are as in
+ * smc_basket_price; columns 16 / 17 use Fb = ((0 + w_0 F_0) + w_1 F_1) + ...
+ * What follows bit for bit: corr_dev with every entry equal to rho is corr_dev = NULL; with that correlation and
+ * equal weights (NULL or explicit 1 / A) terminal_sum_dev and the rainbow columns 2..5, 8..11, 13, 14 are
+ * smc_basket_price's for every A, and the whole block is for A in {1, 2, 4, 8}, where f32(1 / A) is a power of two
+ * (sum (w xs_i) = (sum xs_i) w exactly); stride 0 is the same row materialised B times; lds is replay; run to
+ * run, any split of the batch, the ordinal on the host or on the device.
+ * NORMALIZE parks the terminal values in LDS while A * roundup4(P) * 4 bytes and this kernel's 2112 bytes of
+ * scratch (smc_basket_price's: the factor is built from global memory, the weights stay in registers) fit in
+ * 144 KiB, else simulates a second time; SMC_PRICE_REPLAY forces the latter.
+ * Checks: smc_basket_price's, in its order; then SMC_ERR_INVALID_ARGUMENT for a non-NULL weights_dev whose
+ * weights_stride is neither 0 nor >= A, then for a non-NULL corr_dev whose corr_stride is neither 0 nor
+ * >= A (A - 1) / 2; all before the empty batch (n_contracts = 0: SMC_OK, nothing touched) is accepted.
+ * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  Nothing is validated on the
+ * device, as elsewhere: a matrix that is not positive definite (the factor takes sqrt(max(s, 0)) and divides by
+ * it) or a non-finite weight gives non-finite or meaningless rows; check on the host if the input is not trusted.
+ * Out of scope: Greeks of this basket and sensitivities to correlation entries; weights or a general correlation
+ * in the training targets; a float64 basket engine; path-dependent basket payoffs. */
+int32_t smc_basket_price_general(const double* contracts_dev /*[B][3A+4]*/,
+                                 const double* weights_dev /*rows of A, or NULL*/, int64_t weights_stride,
+                                 const double* corr_dev /*rows of A(A-1)/2, or NULL*/, int64_t corr_stride,
+                                 int64_t n_contracts, int32_t n_assets, int32_t timesteps, int64_t n_paths,
+                                 uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
+                                 int32_t normalization, double* prices_dev /*[B][18]*/,
+                                 double* terminal_sum_dev /*[B][A] or NULL*/, void* stream);
+/* "basket_general_kernel(raw)", "basket_general_kernel(lds)", "basket_general_kernel(replay)" or "unsupported"
+ * (a call smc_basket_price_general rejects).  Static string, no device call. */
+const char* smc_basket_price_general_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                            int32_t normalization);
 
 #ifdef __cplusplus
 }

@@ -19,12 +19,14 @@ record the network, optimizer and Sobol/normal positions as usual but not the ba
 configuration: call ``use_basket_engine`` again on the restored pricer.  ``predict_price``
 stays single-asset; the Monte-Carlo price of a basket (and of the best-of / worst-of payoffs on the
 same paths) comes from ``basket_price`` / ``BasketEngine.price``: one launch of ``smc_basket_price`` for
-B contracts, no terminal buffer in memory.  ``basket_greeks`` / ``BasketEngine.greeks`` give the basket put's and
-call's per-asset deltas and vegas, rho, theta and correlation sensitivity the same way (``smc_basket_greeks``).
+B contracts, no terminal buffer in memory; with ``weights=`` and / or ``correlation=`` the basket has the caller's
+weights and full correlation matrix (``smc_basket_price_general``).  ``basket_greeks`` / ``BasketEngine.greeks``
+give the basket put's and call's per-asset deltas and vegas, rho, theta and correlation sensitivity the same way (``smc_basket_greeks``).
 """
 
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -182,30 +184,130 @@ class BasketPrices:
     block: torch.Tensor
 
 
+def pack_correlation(C: torch.Tensor) -> torch.Tensor:
+    """The strict lower triangle of correlation matrices ``[A, A]`` or ``[B, A, A]``, row by row ((1,0), (2,0),
+    (2,1), (3,0), ...): the ``[A (A - 1) / 2]`` / ``[B, A (A - 1) / 2]`` rows ``smc_basket_price_general`` reads.  On
+    the matrix's device, no host synchronisation; the upper triangle and the diagonal are not looked at."""
+    if C.dim() not in (2, 3) or C.shape[-1] != C.shape[-2]:
+        raise ValueError(f"a correlation matrix must be [A, A] or [B, A, A], got {tuple(C.shape)}")
+    A = C.shape[-1]
+    return C.reshape(C.shape[:-2] + (A * A,)).index_select(-1, _tril_flat(A, C.device)).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def _tril_flat(A: int, device: torch.device) -> torch.Tensor:
+    """Flat indices i A + k of the strict lower triangle in row-major order, on ``device`` (made once per asset
+    count and device, so a later ``pack_correlation`` is device work only and can be captured into a graph)."""
+    rows, cols = np.tril_indices(A, -1)
+    return torch.from_numpy(rows * A + cols).to(device)
+
+
+def _general_weights(weights: torch.Tensor, B: int, A: int) -> tuple[torch.Tensor, int]:
+    """(tensor, stride) of ``basket_price``'s ``weights``: [A] shared (stride 0) or [B, A] (stride A)."""
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or not weights.is_contiguous() or \
+            tuple(weights.shape) not in ((A,), (B, A)):
+        raise ValueError(f"weights must be a contiguous float64 tensor of shape ({A},) or ({B}, {A})")
+    return weights, (0 if weights.dim() == 1 else A)
+
+
+def _general_correlation(corr: torch.Tensor, B: int, A: int) -> tuple[torch.Tensor, int, bool]:
+    """(tensor, stride, packed) of ``basket_price``'s ``correlation``: full matrices [A, A] / [B, A, A] or packed
+    rows [A (A - 1) / 2] / [B, A (A - 1) / 2].  Shapes that read both ways (A = 3: [3, 3] is a matrix and, at
+    B = 3, three packed rows) are taken as matrices."""
+    n = A * (A - 1) // 2
+    full = ((A, A), (B, A, A))
+    if not isinstance(corr, torch.Tensor) or corr.dtype != torch.float64 or not corr.is_contiguous() or \
+            tuple(corr.shape) not in full + ((n,), (B, n)):
+        raise ValueError(f"correlation must be a contiguous float64 tensor of shape ({A}, {A}), ({B}, {A}, {A}), "
+                         f"({n},) or ({B}, {n})")
+    if tuple(corr.shape) in full:
+        return corr, (0 if corr.dim() == 2 else n), False
+    return corr, (0 if corr.dim() == 1 else n), True
+
+
+def validate_basket_inputs(weights: torch.Tensor | None, correlation: torch.Tensor | None, n_assets: int) -> None:
+    """``basket_price(validate=True)``'s checks (they read the values: a host synchronisation for device tensors):
+    ValueError for a non-finite weight, and for a correlation matrix that is asymmetric, has a diagonal other than
+    1 or is not positive definite (``torch.linalg.cholesky_ex``'s info).  Packed rows are unpacked into the
+    symmetric unit-diagonal matrix they stand for, so only the last check can fail for them."""
+    A = n_assets
+    if weights is not None and not bool(torch.isfinite(weights).all()):
+        raise ValueError("weights must be finite")
+    if correlation is None:
+        return
+    C = correlation
+    if not (C.dim() in (2, 3) and C.shape[-1] == A and C.shape[-2] == A):  # packed rows
+        rows, cols = np.tril_indices(A, -1)
+        full = torch.zeros(C.shape[:-1] + (A, A), dtype=C.dtype, device=C.device)
+        full[..., torch.from_numpy(rows).to(C.device), torch.from_numpy(cols).to(C.device)] = C
+        C = full + full.transpose(-1, -2) + torch.eye(A, dtype=C.dtype, device=C.device)
+    if not bool(torch.isfinite(C).all()):
+        raise ValueError("correlation must be finite")
+    if not bool((C == C.transpose(-1, -2)).all()):
+        raise ValueError("correlation must be symmetric")
+    if not bool((torch.diagonal(C, dim1=-2, dim2=-1) == 1.0).all()):
+        raise ValueError("correlation must have a unit diagonal")
+    _, info = torch.linalg.cholesky_ex(C)
+    if bool((info != 0).any()):
+        raise ValueError("correlation must be positive definite")
+
+
 def basket_price(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 0, n_paths: int | None = None,
-                 replay: bool = False) -> BasketPrices:
+                 replay: bool = False, weights: torch.Tensor | None = None, correlation: torch.Tensor | None = None,
+                 validate: bool = False) -> BasketPrices:
     """Monte-Carlo prices of the basket, best-of and worst-of puts and calls of device contracts [B, 3A+4]
     f64: one launch of ``smc_basket_price`` on the current stream, no host synchronisation.  ``cfg`` gives
     n_assets, timesteps, mc_seed, normalize and math; ``n_paths`` (default ``cfg.total_paths``) may be any
-    positive count.  ``replay``: never park the terminal values in LDS (the same bits, for timing)."""
+    positive count.  ``replay``: never park the terminal values in LDS (the same bits, for timing).
+
+    ``weights`` / ``correlation`` (either one given: one launch of ``smc_basket_price_general`` instead):
+    contiguous float64 device tensors.  ``weights`` [A] (shared by every contract) or [B, A]; any finite value,
+    negatives included (spreads), not normalised; None means 1 / A.  ``correlation`` [A, A] or [B, A, A] (packed
+    here with ``pack_correlation``), or already packed [A (A - 1) / 2] / [B, A (A - 1) / 2]; None means the rows'
+    equicorrelation ``rho``, otherwise that column is ignored.  The values are not checked on the device
+    (an indefinite matrix gives non-finite or meaningless rows); ``validate=True`` checks them here first
+    (``validate_basket_inputs``) and is the only path that synchronises."""
     if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
             not contracts.is_contiguous():
         raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
     P = cfg.total_paths if n_paths is None else int(n_paths)
     if P <= 0:
         raise ValueError(f"n_paths must be positive, got {n_paths}")
+    B, A = contracts.shape[0], cfg.n_assets
+    general = weights is not None or correlation is not None
+    w_stride = c_stride = 0
+    packed = True
+    if weights is not None:
+        weights, w_stride = _general_weights(weights, B, A)
+    if correlation is not None:
+        correlation, c_stride, packed = _general_correlation(correlation, B, A)
+    for name, t in (("weights", weights), ("correlation", correlation)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
     _lib.require_device()
     if not contracts.is_cuda:
         raise ValueError("contracts must be a device tensor")
-    B = contracts.shape[0]
+    for name, t in (("weights", weights), ("correlation", correlation)):
+        if t is not None and t.device != contracts.device:
+            raise ValueError(f"{name} must be on the contracts' device")
+    if validate:
+        validate_basket_inputs(weights, correlation, A)
     block = torch.empty((B, _lib.BASKET_PRICE_COLS), dtype=torch.float64, device=contracts.device)
     tsum = torch.empty((B, cfg.n_assets), dtype=torch.float64, device=contracts.device)
     if B > 0:
         math = (_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0)
-        _lib.check(_lib.lib().smc_basket_price(
-            _lib.ptr(contracts), B, cfg.n_assets, cfg.timesteps, P, cfg.mc_seed, None, ordinal0, math,
-            _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW, _lib.ptr(block), _lib.ptr(tsum),
-            _lib.stream_handle()))
+        norm = _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW
+        if general:
+            tri = correlation if packed else pack_correlation(correlation)
+            if tri is not None and tri.numel() == 0:  # A = 1: no entry to read
+                tri = None
+            _lib.check(_lib.lib().smc_basket_price_general(
+                _lib.ptr(contracts), _lib.ptr(weights), w_stride, _lib.ptr(tri), c_stride, B, A, cfg.timesteps, P,
+                cfg.mc_seed, None, ordinal0, math, norm, _lib.ptr(block), _lib.ptr(tsum), _lib.stream_handle()))
+        else:
+            _lib.check(_lib.lib().smc_basket_price(
+                _lib.ptr(contracts), B, cfg.n_assets, cfg.timesteps, P, cfg.mc_seed, None, ordinal0, math,
+                norm, _lib.ptr(block), _lib.ptr(tsum), _lib.stream_handle()))
     return BasketPrices(**{name: block[:, col] for col, name in enumerate(PRICE_FIELDS)}, terminal_sum=tsum,
                         block=block)
 
@@ -404,11 +506,14 @@ class BasketEngine:
             stream))
 
     def price(self, contracts: torch.Tensor | None = None, *, ordinal0: int = 0,
-              n_paths: int | None = None) -> BasketPrices:
+              n_paths: int | None = None, weights: torch.Tensor | None = None,
+              correlation: torch.Tensor | None = None) -> BasketPrices:
         """Monte-Carlo prices (``basket_price``) with the engine's configuration, by default of the contracts
-        of the last enqueued step: the Monte-Carlo side of checking a basket-trained network."""
+        of the last enqueued step: the Monte-Carlo side of checking a basket-trained network.  ``weights`` and
+        ``correlation`` as ``basket_price``'s (the training targets themselves stay equal-weight and
+        equicorrelated)."""
         return basket_price(self.buffers.contracts if contracts is None else contracts, self.cfg, ordinal0=ordinal0,
-                            n_paths=n_paths)
+                            n_paths=n_paths, weights=weights, correlation=correlation)
 
     def greeks(self, contracts: torch.Tensor | None = None, *, ordinal0: int = 0,
                n_paths: int | None = None) -> BasketGreeks:
@@ -429,5 +534,5 @@ def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) ->
 
 
 __all__ = ["BasketConfig", "BasketEngine", "BasketGreeks", "BasketPrices", "basket_fields", "basket_greeks",
-           "basket_greeks_fields", "basket_price", "basket_targets", "default_basket_bounds", "use_basket_engine",
-           "MAX_ASSETS"]
+           "basket_greeks_fields", "basket_price", "basket_targets", "default_basket_bounds", "pack_correlation",
+           "use_basket_engine", "validate_basket_inputs", "MAX_ASSETS"]

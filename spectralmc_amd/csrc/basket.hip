@@ -549,6 +549,221 @@ __global__ __launch_bounds__(kBThreads) void basket_price_kernel(BasketArgs a, d
   }
 }
 
+// ---- weighted, general-correlation basket pricing: basket_general_kernel (smc_basket_price_general) ----
+// basket_price_kernel's geometry, streams, chunk / validity handling, modes and sum orders (restated, not shared:
+// basket_price_kernel's registers stay as they are; the path loop is basket_lane_paths), with two things the
+// caller now supplies per contract.  The correlation matrix: its strict lower triangle, packed row by row
+// ((1,0), (2,0), (2,1), (3,0), ...), goes through cholesky_equicorr's statements with rho replaced by C_ik; no
+// matrix (corr NULL) means C_ik = rho, the same statements on the same values.  The weights: w_i = f32 of the
+// caller's f64 (f32(1 / A) without a row), and the basket is bk = (((0 + w_0 xs_0) + w_1 xs_1) + ...), every
+// operation rounded; mx and mn stay over the unweighted xs_i.  Weights may be negative (spreads) and are not
+// normalised.  Stride 0 shares row 0 of either table with every contract.  Scratch: basket_price_kernel's
+// kBPriceHead doubles (2112 B; the factor is built from global memory, the weights live in registers), so the
+// lds -> replay switch falls at the same P as the price kernel's.  Nothing is validated: an indefinite matrix
+// gives non-finite or meaningless rows.
+struct BasketGeneralArgs {
+  const double* weights;  // rows of A, or NULL
+  int64_t weights_stride;
+  const double* corr;     // rows of A (A - 1) / 2, or NULL
+  int64_t corr_stride;
+};
+constexpr int kBGeneralHead = kBPriceHead;
+constexpr size_t kBGeneralScratch = kBGeneralHead * sizeof(double);
+
+// cholesky_equicorr with C_ik (k < i) from the packed triangle tri, or rho where tri is NULL.
+__device__ void cholesky_general(int A, double rho, const double* tri, double* L) {
+  for (int i = 0; i < A; ++i)
+    for (int k = 0; k <= i; ++k) {
+      double s = i == k ? 1.0 : (tri ? tri[i * (i - 1) / 2 + k] : rho);
+      for (int m = 0; m < k; ++m) s = s - L[i * kMaxAssets + m] * L[k * kMaxAssets + m];
+      L[i * kMaxAssets + k] = i == k ? sqrt(s > 0.0 ? s : 0.0) : s / L[k * kMaxAssets + k];
+    }
+}
+
+template <int A, bool HW, int MODE>
+__global__ __launch_bounds__(kBThreads) void basket_general_kernel(BasketArgs a, BasketGeneralArgs g,
+                                                                   double* __restrict__ prices) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  extern __shared__ double lds[];  // kBGeneralHead doubles of scratch, then (kBPriceLds) the parked block
+  double* Ld = lds + kBWaves * kBPriceSums;     // [8][8]
+  double* wsum = Ld + kMaxAssets * kMaxAssets;  // [kBWaves][A]
+  double* tot = wsum + kBWaves * kMaxAssets;    // [A]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  const int64_t P4 = (P + 3) & ~int64_t{3};  // the parked block's row length
+  v4f* park = reinterpret_cast<v4f*>(lds + kBGeneralHead);
+
+  const double* c = a.contracts + b * (3 * A + 4);
+  const double Tm = c[1], r = c[2], rho = c[3];
+  if (tid == 0) cholesky_general(A, rho, g.corr ? g.corr + b * g.corr_stride : nullptr, Ld);
+  __syncthreads();
+  // per-asset log2-unit coefficients, as basket_kernel
+  const double dt = Tm / static_cast<double>(T);
+  const double sq = sqrt(dt);
+  constexpr double zscale = HW ? PathStream::kNormalScale<true> : 1.0;
+  float ca[A], x0[A], Lb[A][A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double drift = r - d - 0.5 * v * v;
+    ca[i] = static_cast<float>(drift * dt * kBLog2e);
+    const double bi = v * sq * kBLog2e * zscale;
+    x0[i] = static_cast<float>(c[4 + i]);
+#pragma unroll
+    for (int k = 0; k < A; ++k) Lb[i][k] = k <= i ? static_cast<float>(bi * Ld[i * kMaxAssets + k]) : 0.0f;
+  }
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+
+  // payoff constants (basket_price_kernel's) and the weights
+  const float Tf = static_cast<float>(Tm);
+  const float df = math::exp_any(static_cast<float>(-r) * Tf);
+  const float Kf = static_cast<float>(c[0]);
+  float wt[A];  // the same for every lane: kept in scalar registers, beside the path loop's vector ones
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const float w = g.weights ? static_cast<float>(g.weights[b * g.weights_stride + i]) : static_cast<float>(1.0 / A);
+    wt[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w)));
+  }
+  auto forward = [&](int i) {
+    return static_cast<float>(c[4 + i]) * math::exp_any(static_cast<float>(r - c[4 + A + i]) * Tf);
+  };
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = P - chunk - kBPaths * static_cast<int64_t>(tid);
+    return static_cast<int>(left <= 0 ? 0 : (left >= kBPaths ? kBPaths : left));
+  };
+  auto simulate = [&](int64_t chunk, float(&x)[A][kBPaths]) {
+    PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+    basket_lane_paths<A, HW>(s, ca, x0, Lb, T, x);
+  };
+  double v[kBPriceSums];
+#pragma unroll
+  for (int i = 0; i < kBPriceSums; ++i) v[i] = 0.0;
+  auto payoffs = [&](const float(&x)[A][kBPaths], int nvalid, const float(&sc)[A]) {
+    auto pay = [&](float diff) { return static_cast<double>(df * (diff > 0.0f ? diff : 0.0f)); };
+#pragma unroll
+    for (int j = 0; j < kBPaths; ++j) {
+      if (j < nvalid) {
+        float bk = 0.0f, mx = 0.0f, mn = 0.0f;
+#pragma unroll
+        for (int i = 0; i < A; ++i) {
+          const float xs = x[i][j] * sc[i];
+          bk = bk + wt[i] * xs;
+          mx = i == 0 || xs > mx ? xs : mx;
+          mn = i == 0 || xs < mn ? xs : mn;
+        }
+        const double p[6] = {pay(Kf - bk), pay(bk - Kf), pay(Kf - mx), pay(mx - Kf), pay(Kf - mn), pay(mn - Kf)};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          v[i] += p[i];
+          v[6 + i] += p[i] * p[i];
+        }
+        v[12] += static_cast<double>(bk);
+        v[13] += static_cast<double>(mx);
+        v[14] += static_cast<double>(mn);
+        v[15] += bk < Kf ? 1.0 : 0.0;
+      }
+    }
+  };
+
+  // pass 1: the terminal sums (RAW: and the payoffs, scale 1; lds: and the parked values)
+  float sc[A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) sc[i] = 1.0f;
+  double acc[A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) acc[i] = 0.0;
+  for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+    const int nvalid = valid_paths(chunk);
+    if (nvalid > 0) {
+      float x[A][kBPaths];
+      simulate(chunk, x);
+#pragma unroll
+      for (int i = 0; i < A; ++i) {
+        float p = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kBPaths; ++j) p += j < nvalid ? x[i][j] : 0.0f;
+        acc[i] += static_cast<double>(p);
+      }
+      if constexpr (MODE == kBPriceRaw) payoffs(x, nvalid, sc);
+      if constexpr (MODE == kBPriceLds) {
+        // slot (chunk + 4 tid) / 4 of row i: chunk + 4 tid < P, so the slot ends at or before P4
+#pragma unroll
+        for (int i = 0; i < A; ++i)
+          park[(i * P4 + chunk) / kBPaths + tid] = v4f{x[i][0], x[i][1], x[i][2], x[i][3]};
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double w = bwave_sum(acc[i]);
+    if (lane == 0) wsum[wave * A + i] = w;
+  }
+  __syncthreads();
+  if (tid < A) {
+    double sum = 0.0;
+    for (int w = 0; w < kBWaves; ++w) sum += wsum[w * A + tid];
+    tot[tid] = sum;
+    if (a.terminal_sum) a.terminal_sum[b * A + tid] = sum;
+  }
+  if constexpr (MODE != kBPriceRaw) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < A; ++i) sc[i] = forward(i) / static_cast<float>(tot[i] / static_cast<double>(P));
+    // pass 2: the payoffs of the lane's own values, parked or simulated again
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float x[A][kBPaths];
+        if constexpr (MODE == kBPriceLds) {
+#pragma unroll
+          for (int i = 0; i < A; ++i) {
+            const v4f q = park[(i * P4 + chunk) / kBPaths + tid];
+#pragma unroll
+            for (int j = 0; j < kBPaths; ++j) x[i][j] = q[j];
+          }
+        } else {
+          simulate(chunk, x);
+        }
+        payoffs(x, nvalid, sc);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kBPriceSums; ++i) {
+    const double w = bwave_sum(v[i]);
+    if (lane == 0) lds[wave * kBPriceSums + i] = w;
+  }
+  __syncthreads();
+  auto total = [&](int i) {
+    double t = 0.0;
+    for (int w = 0; w < kBWaves; ++w) t += lds[w * kBPriceSums + i];
+    return t;
+  };
+  const double n = static_cast<double>(P);
+  double* out = prices + b * SMC_BASKET_PRICE_COLS;
+  if (tid < 6) {  // a payoff's mean and standard error
+    const double m = total(tid) / n;
+    double se = 0.0;
+    if (P > 1) {
+      const double var = total(6 + tid) - n * m * m;
+      se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+    }
+    out[tid] = m;
+    out[6 + tid] = se;
+  } else if (tid >= 12 && tid < kBPriceSums) {  // means of bk, mx, mn; the exercise share
+    out[tid] = total(tid) / n;
+  } else if (tid == kBPriceSums) {  // intrinsic basket put / call on Fb = ((0 + w_0 F_0) + w_1 F_1) + ...
+    float fb = 0.0f;
+#pragma unroll
+    for (int i = 0; i < A; ++i) fb = fb + wt[i] * forward(i);
+    const float ip = Kf - fb, ic = fb - Kf;
+    out[16] = static_cast<double>(df * (ip > 0.0f ? ip : 0.0f));
+    out[17] = static_cast<double>(df * (ic > 0.0f ? ic : 0.0f));
+  }
+}
+
 // ---- batched basket Greeks: basket_greeks_kernel (smc_basket_greeks) -----------------------------
 // basket_price_kernel's geometry, streams, chunk / validity handling, modes and sum orders (restated, not
 // shared: basket_price_kernel's registers stay as they are; the path loop is basket_lane_paths, which only the
@@ -1506,6 +1721,53 @@ int32_t launch_basket_price(int A, const BasketArgs& a, int mode, size_t lds, do
   }
 }
 
+// basket_general_kernel's mode and dynamic LDS for a shape (host only, no HIP call): basket_price_mode's rule with
+// this kernel's scratch in the park bound; -1: not a call it takes.
+int basket_general_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
+  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
+  *lds = kBGeneralScratch;
+  if (normalization == SMC_NORM_RAW) return kBPriceRaw;
+  if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
+  const size_t park = kBGeneralScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
+  if (park > kBPriceParkBytes) return kBPriceReplay;
+  *lds = park;
+  return kBPriceLds;
+}
+
+template <int A, bool HW>
+int32_t launch_basket_general_k(const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds, double* prices,
+                                hipStream_t stream) {
+  auto kernel = mode == kBPriceRaw   ? basket_general_kernel<A, HW, kBPriceRaw>
+                : mode == kBPriceLds ? basket_general_kernel<A, HW, kBPriceLds>
+                                     : basket_general_kernel<A, HW, kBPriceReplay>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "basket_general_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, g, prices);
+  return check_launch("basket_general_kernel");
+}
+
+template <bool HW>
+int32_t launch_basket_general(int A, const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds,
+                              double* prices, hipStream_t stream) {
+  switch (A) {
+    case 1: return launch_basket_general_k<1, HW>(a, g, mode, lds, prices, stream);
+    case 2: return launch_basket_general_k<2, HW>(a, g, mode, lds, prices, stream);
+    case 3: return launch_basket_general_k<3, HW>(a, g, mode, lds, prices, stream);
+    case 4: return launch_basket_general_k<4, HW>(a, g, mode, lds, prices, stream);
+    case 5: return launch_basket_general_k<5, HW>(a, g, mode, lds, prices, stream);
+    case 6: return launch_basket_general_k<6, HW>(a, g, mode, lds, prices, stream);
+    case 7: return launch_basket_general_k<7, HW>(a, g, mode, lds, prices, stream);
+    case 8: return launch_basket_general_k<8, HW>(a, g, mode, lds, prices, stream);
+    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: n_assets must be in 1..8");
+  }
+}
+
 // basket_greeks_kernel's mode and dynamic LDS for a shape (host only, no HIP call): basket_price_mode's rule with
 // this kernel's scratch in the park bound; -1: not a call it takes.
 int basket_greeks_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
@@ -1686,6 +1948,62 @@ const char* smc_basket_price_kernel(int32_t n_assets, int32_t timesteps, int64_t
     case kBPriceRaw: return "basket_price_kernel(raw)";
     case kBPriceLds: return "basket_price_kernel(lds)";
     case kBPriceReplay: return "basket_price_kernel(replay)";
+    default: return "unsupported";
+  }
+}
+
+int32_t smc_basket_price_general(const double* contracts_dev, const double* weights_dev, int64_t weights_stride,
+                                 const double* corr_dev, int64_t corr_stride, int64_t n_contracts, int32_t n_assets,
+                                 int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                                 int64_t ordinal0, int32_t math, int32_t normalization, double* prices_dev,
+                                 double* terminal_sum_dev, void* stream) {
+  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: contracts_dev is NULL");
+  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: prices_dev is NULL");
+  if (n_assets < 1 || n_assets > kMaxAssets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: n_assets must be in 1..8");
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_basket_price_general: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: bad normalization");
+  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
+    return fail(SMC_ERR_INVALID_SHAPE,
+                "smc_basket_price_general: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
+  if (n_paths >= (int64_t{1} << 40))
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price_general: n_paths too large (>= 2^40)");
+  if (weights_dev && weights_stride != 0 && weights_stride < n_assets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: weights_stride must be 0 or >= n_assets");
+  if (corr_dev && corr_stride != 0 && corr_stride < n_assets * (n_assets - 1) / 2)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_basket_price_general: corr_stride must be 0 or >= n_assets (n_assets - 1) / 2");
+  if (n_contracts == 0) return SMC_OK;
+  size_t lds = 0;
+  const int mode = basket_general_mode(n_assets, n_paths, math, normalization, &lds);
+  BasketArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.normalize = normalization != SMC_NORM_RAW;
+  a.terminal_sum = terminal_sum_dev;
+  // A = 1 has no correlation entry: nothing to read, whatever the caller passed
+  const BasketGeneralArgs g{weights_dev, weights_stride, n_assets > 1 ? corr_dev : nullptr, corr_stride};
+  return (math & SMC_MATH_HW)
+             ? launch_basket_general<true>(n_assets, a, g, mode, lds, prices_dev, as_stream(stream))
+             : launch_basket_general<false>(n_assets, a, g, mode, lds, prices_dev, as_stream(stream));
+}
+
+const char* smc_basket_price_general_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                            int32_t normalization) {
+  size_t lds = 0;
+  if (timesteps <= 0) return "unsupported";
+  switch (basket_general_mode(n_assets, n_paths, math, normalization, &lds)) {
+    case kBPriceRaw: return "basket_general_kernel(raw)";
+    case kBPriceLds: return "basket_general_kernel(lds)";
+    case kBPriceReplay: return "basket_general_kernel(replay)";
     default: return "unsupported";
   }
 }
