@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general */
+#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general; smc_basket_greeks_general (with its _kernel and _cols queries) was added under 21 without a new number: the change is purely additive, no existing entry point moved, and the library ships together with the bindings that load it */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -595,8 +595,8 @@ const char* smc_gbm_greeks_kernel(int32_t timesteps, int64_t n_paths, int32_t sc
  * normalization.  SMC_ERR_INVALID_SHAPE: n_contracts < 0 or >= 2^31, timesteps <= 0, n_paths <= 0 or >= 2^40.
  * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  B below the CU count leaves CUs idle.
  * Out of scope: Greeks of the best-of / worst-of payoffs; gammas and cross-gammas (no diagonal lognormal identity
- * holds for a basket); Greeks of the weighted, general-correlation basket (smc_basket_price_general prices it) and
- * sensitivities to single correlation entries; a float64 basket engine; likelihood-ratio estimators. */
+ * holds for a basket); a float64 basket engine; likelihood-ratio estimators.  The Greeks of the weighted,
+ * general-correlation basket and the sensitivities to single correlation entries are smc_basket_greeks_general, below. */
 int32_t smc_basket_greeks(const double* contracts_dev /*[B][3A+4]*/, int64_t n_contracts, int32_t n_assets,
                           int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
                           int64_t ordinal0, int32_t math, int32_t normalization,
@@ -643,8 +643,8 @@ int32_t smc_basket_greeks_cols(int32_t n_assets);
  * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  Nothing is validated on the
  * device, as elsewhere: a matrix that is not positive definite (the factor takes sqrt(max(s, 0)) and divides by
  * it) or a non-finite weight gives non-finite or meaningless rows; check on the host if the input is not trusted.
- * Out of scope: Greeks of this basket and sensitivities to correlation entries; weights or a general correlation
- * in the training targets; a float64 basket engine; path-dependent basket payoffs. */
+ * Out of scope: weights or a general correlation in the training targets; a float64 basket engine; path-dependent
+ * basket payoffs.  This basket's Greeks and sensitivities to correlation entries: smc_basket_greeks_general, below. */
 int32_t smc_basket_price_general(const double* contracts_dev /*[B][3A+4]*/,
                                  const double* weights_dev /*rows of A, or NULL*/, int64_t weights_stride,
                                  const double* corr_dev /*rows of A(A-1)/2, or NULL*/, int64_t corr_stride,
@@ -656,6 +656,99 @@ int32_t smc_basket_price_general(const double* contracts_dev /*[B][3A+4]*/,
  * (a call smc_basket_price_general rejects).  Static string, no device call. */
 const char* smc_basket_price_general_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
                                             int32_t normalization);
+
+/* ---- Greeks of the weighted, general-correlation basket (additive under ABI 21) ----
+ * smc_basket_greeks for the basket smc_basket_price_general prices: it relates to smc_basket_greeks exactly as
+ * smc_basket_price_general relates to smc_basket_price.  Inputs: weights_dev, weights_stride, corr_dev, corr_stride
+ * with smc_basket_price_general's meaning (w_i = f32 of the caller's f64, f32(1.0 / A) when NULL; the packed strict
+ * lower triangle (1,0), (2,0), (2,1), (3,0), ...; C_ik = the row's rho when NULL; stride 0 shares row 0; nothing read
+ * at A = 1) and its factor L (the Banachiewicz statements on C_ik); everything else is smc_basket_greeks's.
+ * With np = A (A - 1) / 2 pairs, n = 4A + 4 + 2 np, greeks_dev is [B][2n + 4] (2 A^2 + 6 A + 12 doubles):
+ *   0 .. A-1 / A .. 2A-1 delta put / call      2A .. 3A-1 / 3A .. 4A-1 vega put / call
+ *   4A, 4A+1 rho put / call    4A+2, 4A+3 theta put / call
+ *   4A+4 .. 4A+3+np     d put / d C_jk, pair q = j (j - 1) / 2 + k in the packed order (1,0), (2,0), (2,1), (3,0), ...
+ *   4A+4+np .. n-1      d call / d C_jk in the same order
+ *   n .. 2n-1 the standard errors of columns 0 .. n-1 (the price call's formula; 0 at P = 1)
+ *   2n, 2n+1 put / call price: smc_basket_price_general's columns 0 and 1 bit for bit
+ *   2n+2, 2n+3 their standard errors: smc_basket_price_general's columns 6 and 7 bit for bit.
+ * d / d C_jk is the derivative with respect to the pair: C_jk and C_kj move together and the matrix stays symmetric
+ * (it is the derivative in the one packed entry the factor reads).  smc_basket_greeks's correlation column moves all
+ * pairs together in this way, so where every entry equals rho the pair columns sum to it (to rounding).
+ * The drivers do not depend on C: with W = L (driver sums), dW / dC_jk = G^jk W, G^jk = (dL / dC_jk) L^-1 lower
+ * triangular with rows i < j zero, and c_i^jk = d ln x_i / d C_jk follows from the A terminal logs alone.
+ * Per contract, each constant in f64 (every f64 operation rounded, in the order written), then rounded to f32; thread q
+ * of the workgroup takes pair q:
+ *   K, df, F_i, s_i, w_i   exactly smc_basket_price_general's
+ *   mu_i, ix0_i, cv_i, cT, crho, rr, av_i, aT_i   exactly smc_basket_greeks's, Lbar_i = M_ii / tot_i under NORMALIZE
+ *   dL^jk  the derivative of the factor's statements with the seed 1 at (j, k): for i, for m <= i:
+ *          ds = (i == j && m == k ? 1 : 0), then for u < m: ds = ds - (dL_iu L_mu + L_iu dL_mu);
+ *          dL_ii = ds / (2 L_ii),  dL_im = (ds - L_im dL_mm) / L_mm
+ *   G^jk   = dL^jk L^-1, row i from m = i down to 0: g = dL_im, then for u = m + 1 .. i: g = g - G_iu L_um;
+ *          G_im = g / L_mm  (smc_basket_greeks's two recursions with another seed)
+ *   g_im^jk = f32(v_i G_im^jk / v_m) for m <= i
+ *   g0_i^jk = f32(-(v_i gs_i)), gs_i = sum_{m <= i} G_im^jk mu_m T / v_m (from 0, in m order)
+ *          (any v_m == 0: every g and g0 is 0, see the conventions)
+ *   RAW:        ac_i^jk = 0
+ *   NORMALIZE:  M_im = sum_p f64(x_i * L_m) for m <= i (the columns' sum order; M_ii is smc_basket_greeks's sxl_i), and
+ *               ac_i^jk = f32(-((..((f64(g0_i^jk) + f64(g_i0^jk) * (M_i0 / tot_i)) + f64(g_i1^jk) * (M_i1 / tot_i)) ..)
+ *                              + f64(g_ii^jk) * (M_ii / tot_i)))
+ *               from the f32 g and g0 the paths use: minus the x_i-weighted mean of c_i^jk over the paths, because c^jk
+ *               is linear in the logs.
+ * Per path, all in f32, every operation rounded (no fused multiply-add):
+ *   L_i = log(x_i / f32(X0_i))  (the portable f32 log; v_log_f32 times ln 2 under SMC_MATH_HW)
+ *   xs_i = x_i s_i    bk = ((0 + w_0 * xs_0) + w_1 * xs_1) + ...    ip = K - bk > 0    ic = bk - K > 0
+ *   put = df max(K - bk, 0)    call = df max(bk - K, 0)    wt_i = (df * xs_i) * w_i
+ *   hv_i = L_i * cv_i + av_i    hT_i = L_i * cT + aT_i    sT = ((0 + wt_0 * hT_0) + wt_1 * hT_1) + ...
+ *   c_i^jk = (..((g0_i^jk + g_i0^jk * L_0) + g_i1^jk * L_1) ..) + g_ii^jk * L_i     for i >= j
+ *   sC^jk = ((0 + wt_j * (c_j^jk + ac_j^jk)) + wt_{j+1} * (c_{j+1}^jk + ac_{j+1}^jk)) + ...   up to i = A - 1
+ *   delta_i      put: ip ? -(wt_i * ix0_i) : 0    call: ic ? wt_i * ix0_i : 0
+ *   vega_i       put: ip ? -(wt_i * hv_i) : 0     call: ic ? wt_i * hv_i : 0
+ *   rho          put: ip ? -crho : 0              call: ic ? crho : 0
+ *   theta        put: rr * put + (ip ? sT : 0)    call: rr * call - (ic ? sT : 0)
+ *   pair (j, k)  put: ip ? -sC^jk : 0             call: ic ? sC^jk : 0
+ * each cast to f64 and added with its square (f64); a column's sum runs per lane over its chunks and paths in order,
+ * then the wave butterfly, then waves 0..7.  A negative weight flips the signs by itself; nothing takes |w|.
+ * sums_dev (may be NULL) [B][A + A (A + 1) / 2] f64: tot_i (smc_basket_price_general's terminal_sum_dev bit for bit),
+ * then M_im at A + i (i + 1) / 2 + m (M_00, M_10, M_11, M_20, ...; all 0 under RAW).
+ * What follows bit for bit: the price columns and tot as above; lds is replay; run to run, any split of the batch, the
+ * ordinal on the host or on the device; stride 0 is the row materialised B times; corr_dev with every entry equal to
+ * rho is corr_dev = NULL; and with that correlation and equal weights (NULL or explicit 1 / A) the delta, vega, rho and
+ * theta columns with their errors are smc_basket_greeks's for A in {1, 2, 4, 8}, where f32(1 / A) is a power of two.
+ * Conventions (smc_basket_greeks's): v_i == 0 gives vega_i = 0 and its error 0.  Any v_i == 0 with A > 1 writes every
+ * pair column, values and errors, as NaN (computed with g = g0 = 0).  A == 1 has no pair column.  T == 0 drops the cT
+ * term.  P == 1 gives every standard error 0.  Nothing is validated on the device: a matrix that is not positive
+ * definite or a non-finite weight gives non-finite or meaningless rows.
+ * Modes and passes: the n + 2 per-path terms are taken in kernel order (the 4A + 4 delta, vega, rho and theta terms as
+ * columns, then put and call of pair 0, of pair 1, ..., then the two prices) in payoff passes of all of them for
+ * A <= 3, 12 for A = 4 and 8 for A = 5..8, i.e. 1, 1, 1, 3, 6, 8, 10, 12 passes for A = 1..8.  Before them, NORMALIZE
+ * takes one pass for tot and M together (A <= 4) or one for tot and one for M (A >= 5); RAW takes tot with its single
+ * payoff pass (A <= 3) or in a pass of its own (A >= 4).  The first pass simulates; every later one reads the terminal
+ * values parked in LDS (x only), or simulates again (replay, and RAW too): the same values and each column's one order
+ * in every mode.  The parked block is used while A * roundup4(P) * 4 bytes and this kernel's 15968 bytes of scratch
+ * (pass partials, the factor, the pass-1 partials and totals, 64 f32 per-asset and 28 x 80 f32 per-pair constants) fit
+ * in 144 KiB; SMC_PRICE_REPLAY forces replay.
+ * math: 0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY; any other bit is rejected.
+ * Checks, all before the empty batch (n_contracts = 0: SMC_OK, nothing touched) is accepted: smc_basket_greeks's in
+ * its order (NULL contracts_dev, NULL greeks_dev, n_assets, math, normalization: SMC_ERR_INVALID_ARGUMENT; n_contracts,
+ * timesteps, n_paths: SMC_ERR_INVALID_SHAPE), then smc_basket_price_general's two stride checks
+ * (SMC_ERR_INVALID_ARGUMENT), weights first.
+ * Stream-ordered: no allocation, no synchronisation, capturable into a graph.
+ * Out of scope: Greeks of the best-of / worst-of payoffs; gammas and cross-gammas; sensitivities to the weights; a
+ * switch that skips the pair columns; weights or a general correlation in the training targets; a float64 basket
+ * engine; likelihood-ratio estimators. */
+int32_t smc_basket_greeks_general(const double* contracts_dev /*[B][3A+4]*/,
+                                  const double* weights_dev /*rows of A, or NULL*/, int64_t weights_stride,
+                                  const double* corr_dev /*rows of A(A-1)/2, or NULL*/, int64_t corr_stride,
+                                  int64_t n_contracts, int32_t n_assets, int32_t timesteps, int64_t n_paths,
+                                  uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
+                                  int32_t normalization, double* greeks_dev /*[B][2A^2+6A+12]*/,
+                                  double* sums_dev /*[B][A + A(A+1)/2] or NULL*/, void* stream);
+/* "basket_greeks_general_kernel(raw)", "basket_greeks_general_kernel(lds)", "basket_greeks_general_kernel(replay)"
+ * or "unsupported" (a call smc_basket_greeks_general rejects).  Static string, no device call. */
+const char* smc_basket_greeks_general_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                             int32_t normalization);
+/* Doubles per contract of greeks_dev: 2 A^2 + 6 A + 12; -1 for n_assets outside 1..8. */
+int32_t smc_basket_greeks_general_cols(int32_t n_assets);
 
 #ifdef __cplusplus
 }

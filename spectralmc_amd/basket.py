@@ -21,7 +21,9 @@ stays single-asset; the Monte-Carlo price of a basket (and of the best-of / wors
 same paths) comes from ``basket_price`` / ``BasketEngine.price``: one launch of ``smc_basket_price`` for
 B contracts, no terminal buffer in memory; with ``weights=`` and / or ``correlation=`` the basket has the caller's
 weights and full correlation matrix (``smc_basket_price_general``).  ``basket_greeks`` / ``BasketEngine.greeks``
-give the basket put's and call's per-asset deltas and vegas, rho, theta and correlation sensitivity the same way (``smc_basket_greeks``).
+give the basket put's and call's per-asset deltas and vegas, rho, theta and correlation sensitivity the same way
+(``smc_basket_greeks``; with ``weights=`` and / or ``correlation=`` those of the weighted, general-correlation basket, the
+correlation sensitivity per pair: ``smc_basket_greeks_general``).
 """
 
 from __future__ import annotations
@@ -202,6 +204,23 @@ def _tril_flat(A: int, device: torch.device) -> torch.Tensor:
     return torch.from_numpy(rows * A + cols).to(device)
 
 
+def unpack_correlation(tri: torch.Tensor, n_assets: int) -> torch.Tensor:
+    """Packed rows ``[.., A (A - 1) / 2]`` (``pack_correlation``'s order) as symmetric matrices ``[.., A, A]`` with a zero
+    diagonal: entry (j, k) and entry (k, j) both hold the row's value for the pair, so ``pack_correlation`` of the
+    result is ``tri`` again.  The layout of ``BasketGeneralGreeks.correlation_put`` / ``correlation_call``, whose
+    matrix form is the sensitivity to each pair.  On the rows' device, no host synchronisation."""
+    A = n_assets
+    if not 1 <= A <= MAX_ASSETS:
+        raise ValueError(f"n_assets must be in 1..{MAX_ASSETS}, got {n_assets}")
+    if tri.dim() < 1 or tri.shape[-1] != A * (A - 1) // 2:
+        raise ValueError(f"packed rows must end in A (A - 1) / 2 = {A * (A - 1) // 2} entries, got {tuple(tri.shape)}")
+    flat = torch.zeros(tri.shape[:-1] + (A * A,), dtype=tri.dtype, device=tri.device)
+    if A > 1:
+        flat.index_copy_(-1, _tril_flat(A, tri.device), tri)
+    full = flat.reshape(tri.shape[:-1] + (A, A))
+    return full + full.transpose(-1, -2)
+
+
 def _general_weights(weights: torch.Tensor, B: int, A: int) -> tuple[torch.Tensor, int]:
     """(tensor, stride) of ``basket_price``'s ``weights``: [A] shared (stride 0) or [B, A] (stride A)."""
     if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or not weights.is_contiguous() or \
@@ -375,20 +394,125 @@ def _greeks_views(block: torch.Tensor, A: int) -> dict[str, torch.Tensor]:
     return out
 
 
+def basket_general_greeks_fields(n_assets: int) -> tuple[str, ...]:
+    """The names of ``smc_basket_greeks_general``'s 2 A^2 + 6 A + 12 columns in order: ``basket_greeks_fields``'s with
+    the two correlation columns replaced by one per pair in ``pack_correlation``'s order, ``correlation_put_j_k`` for
+    every pair, then ``correlation_call_j_k``."""
+    if not 1 <= n_assets <= MAX_ASSETS:
+        raise ValueError(f"n_assets must be in 1..{MAX_ASSETS}, got {n_assets}")
+    A = n_assets
+    means = tuple(f"{kind}_{side}_{i}" for kind in ("delta", "vega") for side in ("put", "call") for i in range(A))
+    means += tuple(f"{kind}_{side}" for kind in ("rho", "theta") for side in ("put", "call"))
+    means += tuple(f"correlation_{side}_{j}_{k}" for side in ("put", "call") for j in range(A) for k in range(j))
+    return means + tuple(m + "_stderr" for m in means) + ("put", "call", "put_stderr", "call_stderr")
+
+
+@dataclass(frozen=True)
+class BasketGeneralGreeks:
+    """``smc_basket_greeks_general``'s block for B contracts of A assets with the caller's weights and correlation.
+    Every field but the sums is a view of ``block`` [B, 2 A^2 + 6 A + 12] (``basket_general_greeks_fields`` order):
+    ``BasketGreeks``'s fields, except that ``correlation_put`` / ``correlation_call`` and their ``_stderr`` are
+    [B, A (A - 1) / 2], the sensitivity to each pair C_jk = C_kj in ``pack_correlation``'s order
+    (``unpack_correlation`` gives the matrix form).  The prices are ``smc_basket_price_general``'s columns 0, 1, 6, 7
+    bit for bit.  ``terminal_sum`` [B, A] and ``sum_moments`` [B, A (A + 1) / 2] (sum_p x_i ln(x_m / X0_m), m <= i, row
+    by row; 0 under RAW) are the pass-1 sums."""
+    delta_put: torch.Tensor
+    delta_call: torch.Tensor
+    vega_put: torch.Tensor
+    vega_call: torch.Tensor
+    rho_put: torch.Tensor
+    rho_call: torch.Tensor
+    theta_put: torch.Tensor
+    theta_call: torch.Tensor
+    correlation_put: torch.Tensor
+    correlation_call: torch.Tensor
+    delta_put_stderr: torch.Tensor
+    delta_call_stderr: torch.Tensor
+    vega_put_stderr: torch.Tensor
+    vega_call_stderr: torch.Tensor
+    rho_put_stderr: torch.Tensor
+    rho_call_stderr: torch.Tensor
+    theta_put_stderr: torch.Tensor
+    theta_call_stderr: torch.Tensor
+    correlation_put_stderr: torch.Tensor
+    correlation_call_stderr: torch.Tensor
+    put: torch.Tensor
+    call: torch.Tensor
+    put_stderr: torch.Tensor
+    call_stderr: torch.Tensor
+    terminal_sum: torch.Tensor
+    sum_moments: torch.Tensor
+    block: torch.Tensor
+
+
+def _general_greeks_views(block: torch.Tensor, A: int) -> dict[str, torch.Tensor]:
+    """The named views of a [B, 2 A^2 + 6 A + 12] block (the column table of include/spectralmc_hip.h)."""
+    npairs = A * (A - 1) // 2
+    n = 4 * A + 4 + 2 * npairs
+    out: dict[str, torch.Tensor] = {}
+    for suffix, base in (("", 0), ("_stderr", n)):
+        for j, name in enumerate(("delta_put", "delta_call", "vega_put", "vega_call")):
+            out[name + suffix] = block[:, base + j * A:base + (j + 1) * A]
+        for j, name in enumerate(("rho_put", "rho_call", "theta_put", "theta_call")):
+            out[name + suffix] = block[:, base + 4 * A + j]
+        for j, name in enumerate(("correlation_put", "correlation_call")):
+            out[name + suffix] = block[:, base + 4 * A + 4 + j * npairs:base + 4 * A + 4 + (j + 1) * npairs]
+    for j, name in enumerate(("put", "call", "put_stderr", "call_stderr")):
+        out[name] = block[:, 2 * n + j]
+    return out
+
+
 def basket_greeks(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 0, n_paths: int | None = None,
-                  replay: bool = False) -> BasketGreeks:
+                  replay: bool = False, weights: torch.Tensor | None = None, correlation: torch.Tensor | None = None,
+                  validate: bool = False) -> BasketGreeks | BasketGeneralGreeks:
     """Pathwise Greeks of the equal-weight basket put and call of device contracts [B, 3A+4] f64: one launch of
-    ``smc_basket_greeks`` on the current stream, no host synchronisation.  Arguments as ``basket_price``."""
+    ``smc_basket_greeks`` on the current stream, no host synchronisation.  Arguments as ``basket_price``.
+
+    ``weights`` / ``correlation`` (either one given: one launch of ``smc_basket_greeks_general`` instead, returning
+    ``BasketGeneralGreeks``): ``basket_price``'s arguments, with its meaning, shapes and checks.  The deltas and vegas
+    are then those of the weighted basket (a negative weight flips their sign by itself) and the correlation
+    sensitivity is reported per pair.  ``validate=True`` checks the values first (``validate_basket_inputs``) and is
+    the only path that synchronises."""
     if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
             not contracts.is_contiguous():
         raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
     P = cfg.total_paths if n_paths is None else int(n_paths)
     if P <= 0:
         raise ValueError(f"n_paths must be positive, got {n_paths}")
+    B, A = contracts.shape[0], cfg.n_assets
+    general = weights is not None or correlation is not None
+    w_stride = c_stride = 0
+    packed = True
+    if weights is not None:
+        weights, w_stride = _general_weights(weights, B, A)
+    if correlation is not None:
+        correlation, c_stride, packed = _general_correlation(correlation, B, A)
+    for name, t in (("weights", weights), ("correlation", correlation)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
     _lib.require_device()
     if not contracts.is_cuda:
         raise ValueError("contracts must be a device tensor")
-    B, A = contracts.shape[0], cfg.n_assets
+    for name, t in (("weights", weights), ("correlation", correlation)):
+        if t is not None and t.device != contracts.device:
+            raise ValueError(f"{name} must be on the contracts' device")
+    if validate:
+        validate_basket_inputs(weights, correlation, A)
+    if general:
+        block = torch.empty((B, _lib.basket_greeks_general_cols(A)), dtype=torch.float64, device=contracts.device)
+        nm = A * (A + 1) // 2
+        sums = torch.empty((B, A + nm), dtype=torch.float64, device=contracts.device)
+        if B > 0:
+            math = (_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0)
+            tri = correlation if packed else pack_correlation(correlation)
+            if tri is not None and tri.numel() == 0:  # A = 1: no entry to read
+                tri = None
+            _lib.check(_lib.lib().smc_basket_greeks_general(
+                _lib.ptr(contracts), _lib.ptr(weights), w_stride, _lib.ptr(tri), c_stride, B, A, cfg.timesteps, P,
+                cfg.mc_seed, None, ordinal0, math, _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW,
+                _lib.ptr(block), _lib.ptr(sums), _lib.stream_handle()))
+        return BasketGeneralGreeks(**_general_greeks_views(block, A), terminal_sum=sums[:, :A], sum_moments=sums[:, A:],
+                                   block=block)
     block = torch.empty((B, _lib.basket_greeks_cols(A)), dtype=torch.float64, device=contracts.device)
     sums = torch.empty((B, 3, A), dtype=torch.float64, device=contracts.device)
     if B > 0:
@@ -516,11 +640,12 @@ class BasketEngine:
                             n_paths=n_paths, weights=weights, correlation=correlation)
 
     def greeks(self, contracts: torch.Tensor | None = None, *, ordinal0: int = 0,
-               n_paths: int | None = None) -> BasketGreeks:
+               n_paths: int | None = None, weights: torch.Tensor | None = None,
+               correlation: torch.Tensor | None = None, validate: bool = False) -> BasketGreeks | BasketGeneralGreeks:
         """Pathwise Greeks (``basket_greeks``) with the engine's configuration, by default of the contracts of the
-        last enqueued step."""
+        last enqueued step.  ``weights``, ``correlation`` and ``validate`` as ``basket_greeks``'s."""
         return basket_greeks(self.buffers.contracts if contracts is None else contracts, self.cfg, ordinal0=ordinal0,
-                             n_paths=n_paths)
+                             n_paths=n_paths, weights=weights, correlation=correlation, validate=validate)
 
 
 def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) -> None:
@@ -533,6 +658,7 @@ def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) ->
     pricer.mc_engine_factory = factory
 
 
-__all__ = ["BasketConfig", "BasketEngine", "BasketGreeks", "BasketPrices", "basket_fields", "basket_greeks",
-           "basket_greeks_fields", "basket_price", "basket_targets", "default_basket_bounds", "pack_correlation",
-           "use_basket_engine", "validate_basket_inputs", "MAX_ASSETS"]
+__all__ = ["BasketConfig", "BasketEngine", "BasketGeneralGreeks", "BasketGreeks", "BasketPrices", "basket_fields",
+           "basket_general_greeks_fields", "basket_greeks", "basket_greeks_fields", "basket_price", "basket_targets",
+           "default_basket_bounds", "pack_correlation", "unpack_correlation", "use_basket_engine",
+           "validate_basket_inputs", "MAX_ASSETS"]

@@ -1166,6 +1166,445 @@ __global__ __launch_bounds__(kBThreads) void basket_greeks_kernel(BasketArgs a, 
   }
 }
 
+// ---- Greeks of the weighted, general-correlation basket: basket_greeks_general_kernel (smc_basket_greeks_general) ----
+// basket_greeks_kernel with basket_general_kernel's two inputs (restated, not shared: the kernels above keep their
+// registers): the factor is cholesky_general's, the basket is bk = ((0 + w_0 xs_0) + w_1 xs_1) + ... and a term's
+// weight is (df xs_i) w_i.  The one correlation column becomes one per pair (j, k), k < j, in pack_correlation's
+// order: d / dC_jk with the matrix kept symmetric, which is the derivative in the one entry the factor reads.  The
+// drivers do not depend on C, so dW / dC_jk = G^jk W with G^jk = (dL / dC_jk) L^-1, and c_i^jk = g0_i^jk +
+// sum_{m <= i} g_im^jk L_m is d ln x_i / dC_jk from the A terminal logs; rows i < j of G^jk are zero.  Thread q < np
+// differentiates the Banachiewicz statements for pair q (seed 1 at (j, k)) and solves G L = dL in f64 (one thread per
+// pair, not the one thread that factors: 28 pairs in turn would cost a contract some 10^4 dependent LDS round trips),
+// then leaves g^q, g0^q (and later ac^q) in LDS as f32.  Under NORMALIZE every ac_i^jk follows per contract from the
+// A (A + 1) / 2 moment sums M_im = sum_p f64(x_i L_m), m <= i (M_ii is basket_greeks_kernel's sxl_i).
+// Terms per path: NT = 4A + 6 + A (A - 1); kernel order: the 4A + 4 delta, vega, rho and theta terms as columns, then
+// (put, call) of pair 0, of pair 1, ..., then the two prices; they are taken basket_ggreek_pass_terms(A) at a time.
+constexpr int basket_ggreek_pairs(int A) { return A * (A - 1) / 2; }
+constexpr int basket_ggreek_terms(int A) { return 4 * A + 6 + 2 * basket_ggreek_pairs(A); }
+constexpr int basket_ggreek_pass_terms(int A) { return A <= 3 ? basket_ggreek_terms(A) : (A == 4 ? 12 : 8); }
+constexpr int kBGGRed = 2 * basket_ggreek_terms(3);     // the widest pass: 24 terms and their squares
+constexpr int kBGGMaxPairs = basket_ggreek_pairs(kMaxAssets);                 // 28
+constexpr int kBGGSums = kMaxAssets + kMaxAssets * (kMaxAssets + 1) / 2;      // tot [8], M packed [36]
+constexpr int kBGGFc = 8;                               // f32 constants per asset: s, ix0, cv, av, aT
+constexpr int kBGGPc = kMaxAssets * kMaxAssets + 2 * kMaxAssets;  // f32 per pair: g [8][8], g0 [8], ac [8]
+// scratch at the head of the dynamic LDS (f64): pass-sum partials [kBWaves][kBGGRed], L [8][8], pass-1 partials
+// [kBWaves][kBGGSums] and totals [kBGGSums], then the f32 constants [8][kBGGFc] and [28][kBGGPc]
+// (15968 B, a multiple of 16)
+constexpr int kBGGHead = kBWaves * kBGGRed + kMaxAssets * kMaxAssets + kBWaves * kBGGSums + kBGGSums +
+                         (kMaxAssets * kBGGFc + kBGGMaxPairs * kBGGPc) / 2;
+constexpr size_t kBGGScratch = kBGGHead * sizeof(double);
+static_assert(kBGGScratch == 15968 && kBGGScratch % 16 == 0, "the header states the scratch bytes");
+
+constexpr int basket_ggreek_pair_row(int q) {  // j of packed pair q = j (j - 1) / 2 + k
+  int j = 1;
+  while ((j + 1) * j / 2 <= q) ++j;
+  return j;
+}
+
+// The f32 constants g^q, g0^q of pair q = (pj, pk) into its slice p of kBGGPc floats (ac^q = 0): dL / dC_jk by
+// cholesky_equicorr_drho's statements with the seed 1 at (pj, pk) and 0 elsewhere, then G = dL L^-1 row by row.  f64,
+// one thread, L in LDS with row stride 8.  dL is kept in the slice itself, packed row by row as f64 (36 of its 40
+// doubles), and G one row at a time in registers: the rows are taken from the last to the first, so the floats of
+// row i (doubles 4 i .. 4 i + 3, and 32 + i / 2 for g0) only overwrite dL rows already used (row i ends at double
+// i (i + 1) / 2 + i <= 4 i + 3, and row 7 is used first).  Every loop is unrolled: all LDS offsets are constants.
+template <int A>
+__device__ __forceinline__ void cholesky_general_dpair(const double* L, int pj, int pk, const double* c, double r,
+                                                       double Tm, bool anyv0, float* p) {
+  double* dL = reinterpret_cast<double*>(p);
+#pragma unroll
+  for (int i = 0; i < A; ++i)
+#pragma unroll
+    for (int k = 0; k <= i; ++k) {
+      double ds = (i == pj && k == pk) ? 1.0 : 0.0;
+#pragma unroll
+      for (int m = 0; m < k; ++m)
+        ds = ds - (dL[i * (i + 1) / 2 + m] * L[k * kMaxAssets + m] + L[i * kMaxAssets + m] * dL[k * (k + 1) / 2 + m]);
+      dL[i * (i + 1) / 2 + k] = i == k ? ds / (2.0 * L[i * kMaxAssets + i])
+                                       : (ds - L[i * kMaxAssets + k] * dL[k * (k + 1) / 2 + k]) / L[k * kMaxAssets + k];
+    }
+#pragma unroll
+  for (int i = A - 1; i >= 0; --i) {
+    double G[A];
+#pragma unroll
+    for (int k = i; k >= 0; --k) {
+      double g = dL[i * (i + 1) / 2 + k];
+#pragma unroll
+      for (int m = k + 1; m <= i; ++m) g = g - G[m] * L[m * kMaxAssets + k];
+      G[k] = g / L[k * kMaxAssets + k];
+    }
+    asm volatile("" ::: "memory");  // the f32 stores below reuse the f64 row just read
+    const double vi = c[4 + 2 * A + i];
+    double gs = 0.0;
+#pragma unroll
+    for (int m = 0; m <= i; ++m) {
+      const double vm = c[4 + 2 * A + m];
+      const double mum = r - c[4 + A + m] - 0.5 * vm * vm;
+      gs = gs + G[m] * mum * Tm / vm;
+      p[i * kMaxAssets + m] = anyv0 ? 0.0f : static_cast<float>(vi * G[m] / vm);
+    }
+    p[kMaxAssets * kMaxAssets + i] = anyv0 ? 0.0f : static_cast<float>(-(vi * gs));
+    asm volatile("" ::: "memory");
+  }
+#pragma unroll
+  for (int i = 0; i < A; ++i) p[kMaxAssets * kMaxAssets + kMaxAssets + i] = 0.0f;
+}
+
+template <int A, bool HW, int MODE>
+__global__ __launch_bounds__(kBThreads) void basket_greeks_general_kernel(BasketArgs a, BasketGeneralArgs g,
+                                                                          double* __restrict__ greeks,
+                                                                          double* __restrict__ sums) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  constexpr int NPR = basket_ggreek_pairs(A);      // pairs
+  constexpr int NT = basket_ggreek_terms(A);       // per-path terms
+  constexpr int TP = basket_ggreek_pass_terms(A);  // terms per payoff pass
+  constexpr int NP = (NT + TP - 1) / TP;           // payoff passes
+  constexpr int NG = NT - 2;                       // Greek columns n = 4A + 4 + 2 np
+  constexpr int NM = A * (A + 1) / 2;              // moment sums
+  constexpr int PT0 = 4 * A + 4;                   // the first pair term
+  static_assert(2 * TP <= kBGGRed, "pass partials");
+  extern __shared__ double lds[];  // kBGGHead doubles of scratch, then (kBPriceLds) the parked block
+  double* Ld = lds + kBWaves * kBGGRed;           // [8][8]
+  double* wsum = Ld + kMaxAssets * kMaxAssets;    // [kBWaves][kBGGSums]
+  double* tot = wsum + kBWaves * kBGGSums;        // [kBGGSums]: tot [8], M_im at 8 + i (i + 1) / 2 + m
+  float* fc = reinterpret_cast<float*>(tot + kBGGSums);  // [8][kBGGFc]
+  float* pc = fc + kMaxAssets * kBGGFc;           // [28][kBGGPc]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  const int64_t P4 = (P + 3) & ~int64_t{3};  // the parked block's row length
+  v4f* park = reinterpret_cast<v4f*>(lds + kBGGHead);
+
+  const double* c = a.contracts + b * (3 * A + 4);
+  const double Tm = c[1], r = c[2], rho = c[3];
+  if (tid == 0) cholesky_general(A, rho, g.corr ? g.corr + b * g.corr_stride : nullptr, Ld);
+  __syncthreads();
+  bool anyv0 = false;
+#pragma unroll
+  for (int i = 0; i < A; ++i) anyv0 = anyv0 || c[4 + 2 * A + i] == 0.0;
+  // Thread q < np: g^q, g0^q of its pair (ac^q = 0 until the sums are known).  A deterministic asset (some v == 0)
+  // leaves no driver to recover: g = g0 = 0, the pair columns NaN.
+  if constexpr (NPR > 0) {
+    if (tid < NPR) {
+      int pj = 1;
+      while ((pj + 1) * pj / 2 <= tid) ++pj;
+      cholesky_general_dpair<A>(Ld, pj, tid - pj * (pj - 1) / 2, c, r, Tm, anyv0, pc + tid * kBGGPc);
+    }
+  }
+  // per-asset log2-unit coefficients, as basket_kernel
+  const double dt = Tm / static_cast<double>(T);
+  const double sq = sqrt(dt);
+  constexpr double zscale = HW ? PathStream::kNormalScale<true> : 1.0;
+  float ca[A], x0[A], Lb[A][A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double drift = r - d - 0.5 * v * v;
+    ca[i] = static_cast<float>(drift * dt * kBLog2e);
+    const double bi = v * sq * kBLog2e * zscale;
+    x0[i] = static_cast<float>(c[4 + i]);
+#pragma unroll
+    for (int k = 0; k < A; ++k) Lb[i][k] = k <= i ? static_cast<float>(bi * Ld[i * kMaxAssets + k]) : 0.0f;
+  }
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+
+  // payoff constants (basket_general_kernel's), the weights and the scalar constants of the table
+  const float Tf = static_cast<float>(Tm);
+  const float df = math::exp_any(static_cast<float>(-r) * Tf);
+  const float Kf = static_cast<float>(c[0]);
+  float wt[A];  // the same for every lane: kept in scalar registers
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const float w = g.weights ? static_cast<float>(g.weights[b * g.weights_stride + i]) : static_cast<float>(1.0 / A);
+    wt[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w)));
+  }
+  const float cT = Tm == 0.0 ? 0.0f : static_cast<float>(1.0 / (2.0 * Tm));
+  const float crho = df * (Tf * Kf);
+  const float rr = static_cast<float>(r);
+  auto forward = [&](int i) {
+    return static_cast<float>(c[4 + i]) * math::exp_any(static_cast<float>(r - c[4 + A + i]) * Tf);
+  };
+  // the constants that need no sum, per asset: ix0, cv and RAW's s, av, aT (a wave the pairs above do not hold up)
+  if (tid >= 64 && tid < 64 + A) {
+    const int i = tid - 64;
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double mu = r - d - 0.5 * v * v;
+    float* f = fc + i * kBGGFc;
+    f[0] = 1.0f;
+    f[1] = static_cast<float>(1.0 / c[4 + i]);
+    f[2] = v == 0.0 ? 0.0f : static_cast<float>(1.0 / v);
+    f[3] = v == 0.0 ? 0.0f : static_cast<float>(-mu * Tm / v - v * Tm);
+    f[4] = static_cast<float>(mu / 2.0);
+  }
+  __syncthreads();
+
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = P - chunk - kBPaths * static_cast<int64_t>(tid);
+    return static_cast<int>(left <= 0 ? 0 : (left >= kBPaths ? kBPaths : left));
+  };
+  auto simulate = [&](int64_t chunk, float(&x)[A][kBPaths]) {
+    PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+    basket_lane_paths<A, HW>(s, ca, x0, Lb, T, x);
+  };
+  auto load_parked = [&](int64_t chunk, float(&x)[A][kBPaths]) {  // the lane's own values: no barrier needed
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+      const v4f q = park[(i * P4 + chunk) / kBPaths + tid];
+#pragma unroll
+      for (int j = 0; j < kBPaths; ++j) x[i][j] = q[j];
+    }
+  };
+  // terminal sums of one chunk in basket_price_kernel's order
+  auto add_terminal = [&](const float(&x)[A][kBPaths], int nvalid, double(&acc)[A]) {
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+      float p = 0.0f;
+#pragma unroll
+      for (int j = 0; j < kBPaths; ++j) p += j < nvalid ? x[i][j] : 0.0f;
+      acc[i] += static_cast<double>(p);
+    }
+  };
+  // a lane's partials of n pass-1 sums from slot s0 on through the wave butterfly; finish_sums then adds waves 0..7
+  // of tot and (with_m) of M (else 0) and reports them
+  auto wave_sums = [&](const auto& acc, int s0) {
+    constexpr int n = static_cast<int>(sizeof(acc) / sizeof(double));
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      const double w = bwave_sum(acc[i]);
+      if (lane == 0) wsum[wave * kBGGSums + s0 + i] = w;
+    }
+  };
+  auto finish_sums = [&](bool with_m) {
+    __syncthreads();
+    if (tid < kBGGSums) {
+      const bool is_m = tid >= kMaxAssets;
+      const int p = is_m ? tid - kMaxAssets : tid;
+      if (p < (is_m ? NM : A)) {
+        double sum = 0.0;
+        if (!is_m || with_m)
+          for (int w = 0; w < kBWaves; ++w) sum += wsum[w * kBGGSums + tid];
+        tot[tid] = sum;
+        if (sums) sums[b * (A + NM) + (is_m ? A : 0) + p] = sum;
+      }
+    }
+    __syncthreads();
+  };
+  // One pass over the paths for the sums that come before the payoffs: TOT the terminal sums (the first pass over
+  // the paths: it simulates and, in the lds mode, parks), MOM the moments M_im = sum f64(x_i L_m), m <= i.  A <= 4
+  // takes both together; from A = 5 on TOT goes first, alone (basket_greeks_kernel's plan).
+  auto sum_pass = [&](auto tot_tag, auto mom_tag) {
+    constexpr bool TOT = decltype(tot_tag)::value, MOM = decltype(mom_tag)::value;
+    double acc[A], accm[NM];
+#pragma unroll
+    for (int i = 0; i < A; ++i) acc[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NM; ++i) accm[i] = 0.0;
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float x[A][kBPaths];
+        if constexpr (MODE == kBPriceLds && !TOT) load_parked(chunk, x);
+        else simulate(chunk, x);
+        if constexpr (TOT) add_terminal(x, nvalid, acc);
+        if constexpr (MOM) {
+#pragma unroll
+          for (int j = 0; j < kBPaths; ++j) {
+            if (j < nvalid) {
+              float L[A];
+#pragma unroll
+              for (int i = 0; i < A; ++i) L[i] = basket_greeks_log<HW>(x[i][j], x0[i]);
+#pragma unroll
+              for (int i = 0; i < A; ++i)
+#pragma unroll
+                for (int m = 0; m <= i; ++m) accm[i * (i + 1) / 2 + m] += static_cast<double>(x[i][j] * L[m]);
+            }
+          }
+        }
+        if constexpr (MODE == kBPriceLds && TOT) {
+          // slot (chunk + 4 tid) / 4 of row i: chunk + 4 tid < P, so the slot ends at or before P4
+#pragma unroll
+          for (int i = 0; i < A; ++i)
+            park[(i * P4 + chunk) / kBPaths + tid] = v4f{x[i][0], x[i][1], x[i][2], x[i][3]};
+        }
+      }
+    }
+    if constexpr (TOT) wave_sums(acc, 0);
+    if constexpr (MOM) wave_sums(accm, kMaxAssets);
+  };
+  constexpr bool kSplitRaw = NP > 1;  // RAW: the terminal sums ride along with a single payoff pass only
+  constexpr bool kSplitMom = A > 4;
+  using yes = std::true_type;
+  using no = std::false_type;
+
+  if constexpr (MODE != kBPriceRaw) {
+    if constexpr (kSplitMom) {
+      sum_pass(yes{}, no{});
+      sum_pass(no{}, yes{});
+    } else {
+      sum_pass(yes{}, yes{});
+    }
+    finish_sums(true);
+    if (tid >= 256 && tid < 256 + A) {  // the per-asset constants that move with the sums
+      const int i = tid - 256;
+      const double v = c[4 + 2 * A + i], rd = r - c[4 + A + i];
+      const double lbar = tot[kMaxAssets + i * (i + 1) / 2 + i] / tot[i];
+      float* f = fc + i * kBGGFc;
+      f[0] = forward(i) / static_cast<float>(tot[i] / static_cast<double>(P));
+      f[3] = v == 0.0 ? 0.0f : static_cast<float>(-lbar / v);
+      f[4] = Tm == 0.0 ? static_cast<float>(rd) : static_cast<float>(-lbar / (2.0 * Tm) + rd);
+    }
+    if (tid < NPR * kMaxAssets) {  // ac_i^q of pair q = tid / 8, asset i = tid % 8, from the f32 g^q, g0^q the paths see
+      const int q = tid >> 3, i = tid & 7;
+      if (i < A) {
+        float* p = pc + q * kBGGPc;
+        double s = static_cast<double>(p[kMaxAssets * kMaxAssets + i]);
+        for (int m = 0; m <= i; ++m)
+          s = s + static_cast<double>(p[i * kMaxAssets + m]) * (tot[kMaxAssets + i * (i + 1) / 2 + m] / tot[i]);
+        p[kMaxAssets * kMaxAssets + kMaxAssets + i] = static_cast<float>(-s);
+      }
+    }
+    __syncthreads();
+  } else if constexpr (kSplitRaw) {  // RAW with several payoff passes: the terminal sums in a pass of their own
+    sum_pass(yes{}, no{});
+    finish_sums(false);
+  }
+
+  // one path's terms of pass PASS (the table of the header), each cast to f64 and added with its square
+  double v[2 * TP];
+  auto payoffs = [&](auto tag, const float(&x)[A][kBPaths], int nvalid) {
+    constexpr int T0 = decltype(tag)::value * TP;
+    constexpr int T1 = T0 + TP < NT ? T0 + TP : NT;
+    constexpr bool kTheta = T0 <= 4 * A + 3 && T1 > 4 * A + 2;
+#pragma unroll
+    for (int j = 0; j < kBPaths; ++j) {
+      if (j < nvalid) {
+        // from A = 4 on the LDS constants are read again for every path, not held across the path loop
+        if constexpr (A > 3) asm volatile("" ::: "memory");
+        float L[A], w[A];
+        float bk = 0.0f;
+#pragma unroll
+        for (int i = 0; i < A; ++i) {
+          const float xs = x[i][j] * fc[i * kBGGFc];
+          bk = bk + wt[i] * xs;
+          w[i] = (df * xs) * wt[i];
+          L[i] = basket_greeks_log<HW>(x[i][j], x0[i]);
+        }
+        const float dp = Kf - bk, dc = bk - Kf;
+        const bool ip = dp > 0.0f, ic = dc > 0.0f;
+        const float put = df * (ip ? dp : 0.0f), call = df * (ic ? dc : 0.0f);
+        float sT = 0.0f;
+        if constexpr (kTheta) {
+#pragma unroll
+          for (int i = 0; i < A; ++i) sT = sT + w[i] * (L[i] * cT + fc[i * kBGGFc + 4]);
+        }
+        // sC^q = ((0 + w_j hc_j) + w_{j+1} hc_{j+1}) + ..., hc_i = c_i^q + ac_i^q, rows i >= j of pair q = (j, k)
+        auto pair_sum = [&](auto qtag) {
+          constexpr int q = decltype(qtag)::value;
+          constexpr int pj = basket_ggreek_pair_row(q);
+          const float* p = pc + q * kBGGPc;
+          float sC = 0.0f;
+#pragma unroll
+          for (int i = pj; i < A; ++i) {
+            float ci = p[kMaxAssets * kMaxAssets + i];
+#pragma unroll
+            for (int m = 0; m <= i; ++m) ci = ci + p[i * kMaxAssets + m] * L[m];
+            sC = sC + w[i] * (ci + p[kMaxAssets * kMaxAssets + kMaxAssets + i]);
+          }
+          return sC;
+        };
+        basket_static_for(std::make_integer_sequence<int, T1 - T0>{}, [&](auto ktag) {
+          constexpr int k = decltype(ktag)::value;
+          constexpr int term = T0 + k;
+          float t;
+          if constexpr (term < 4 * A) {
+            constexpr int kind = term / A, i = term % A;  // 0 delta put, 1 delta call, 2 vega put, 3 vega call
+            const float* f = fc + i * kBGGFc;
+            const float wx = kind < 2 ? w[i] * f[1] : w[i] * (L[i] * f[2] + f[3]);
+            t = (kind & 1) ? (ic ? wx : 0.0f) : (ip ? -wx : 0.0f);
+          } else if constexpr (term == 4 * A) {
+            t = ip ? -crho : 0.0f;
+          } else if constexpr (term == 4 * A + 1) {
+            t = ic ? crho : 0.0f;
+          } else if constexpr (term == 4 * A + 2) {
+            t = rr * put + (ip ? sT : 0.0f);
+          } else if constexpr (term == 4 * A + 3) {
+            t = rr * call - (ic ? sT : 0.0f);
+          } else if constexpr (term < NG) {
+            const float sC = pair_sum(std::integral_constant<int, (term - PT0) / 2>{});
+            t = ((term - PT0) & 1) ? (ic ? sC : 0.0f) : (ip ? -sC : 0.0f);
+          } else {
+            t = term == NG ? put : call;
+          }
+          const double d = static_cast<double>(t);
+          v[k] += d;
+          v[TP + k] += d * d;
+        });
+      }
+    }
+  };
+
+  const double n = static_cast<double>(P);
+  double* out = greeks + b * (2 * NG + 4);
+#pragma unroll 1
+  for (int pass = 0; pass < NP; ++pass) {
+#pragma unroll
+    for (int k = 0; k < 2 * TP; ++k) v[k] = 0.0;
+    double acc[A];  // RAW with one payoff pass: the terminal sums ride along
+#pragma unroll
+    for (int i = 0; i < A; ++i) acc[i] = 0.0;
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float x[A][kBPaths];
+        if constexpr (MODE == kBPriceLds) load_parked(chunk, x);
+        else simulate(chunk, x);
+        if constexpr (MODE == kBPriceRaw && !kSplitRaw) add_terminal(x, nvalid, acc);
+        basket_static_for(std::make_integer_sequence<int, NP>{}, [&](auto tag) {
+          if (NP == 1 || pass == decltype(tag)::value) payoffs(tag, x, nvalid);
+        });
+      }
+    }
+    if constexpr (MODE == kBPriceRaw && !kSplitRaw) {
+      wave_sums(acc, 0);
+      finish_sums(false);  // M = 0
+    }
+    // the pass's sums: wave butterfly, waves 0..7, sum k totalled by thread k
+#pragma unroll
+    for (int k = 0; k < 2 * TP; ++k) {
+      const double w = bwave_sum(v[k]);
+      if (lane == 0) lds[wave * kBGGRed + k] = w;
+    }
+    __syncthreads();
+    const int term = pass * TP + tid;
+    if (tid < TP && term < NT) {  // a term's mean and standard error
+      auto total = [&](int k) {
+        double t2 = 0.0;
+        for (int w = 0; w < kBWaves; ++w) t2 += lds[w * kBGGRed + k];
+        return t2;
+      };
+      double m = total(tid) / n;
+      double se = 0.0;
+      if (P > 1) {
+        const double var = total(TP + tid) - n * m * m;
+        se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+      }
+      if (term < PT0) {
+        out[term] = m;
+        out[NG + term] = se;
+      } else if (term < NG) {  // pair q, put at 4A + 4 + q, call at 4A + 4 + np + q
+        if (anyv0) m = se = __builtin_nan("");
+        const int col = PT0 + ((term - PT0) & 1) * NPR + ((term - PT0) >> 1);
+        out[col] = m;
+        out[NG + col] = se;
+      } else {  // the prices: columns 2n, 2n + 1 and 2n + 2, 2n + 3
+        out[NG + term] = m;
+        out[NG + term + 2] = se;
+      }
+    }
+    if (NP > 1) __syncthreads();  // the partials are rewritten by the next pass
+  }
+}
+
 
 // ---- basket_resident_kernel: the terminal rows never leave the chip ------------------------------
 // A C5 contract's terminal rows are A x P f32 = 2 MiB, far beyond one CU, so W = P / 4096
@@ -1815,6 +2254,54 @@ int32_t launch_basket_greeks(int A, const BasketArgs& a, int mode, size_t lds, d
   }
 }
 
+// basket_greeks_general_kernel's mode and dynamic LDS for a shape (host only, no HIP call): basket_price_mode's rule
+// with this kernel's scratch in the park bound; -1: not a call it takes.
+int basket_greeks_general_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
+  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
+  *lds = kBGGScratch;
+  if (normalization == SMC_NORM_RAW) return kBPriceRaw;
+  if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
+  const size_t park = kBGGScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
+  if (park > kBPriceParkBytes) return kBPriceReplay;
+  *lds = park;
+  return kBPriceLds;
+}
+
+template <int A, bool HW>
+int32_t launch_basket_greeks_general_k(const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds,
+                                       double* greeks, double* sums, hipStream_t stream) {
+  auto kernel = mode == kBPriceRaw   ? basket_greeks_general_kernel<A, HW, kBPriceRaw>
+                : mode == kBPriceLds ? basket_greeks_general_kernel<A, HW, kBPriceLds>
+                                     : basket_greeks_general_kernel<A, HW, kBPriceReplay>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "basket_greeks_general_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, g, greeks,
+         sums);
+  return check_launch("basket_greeks_general_kernel");
+}
+
+template <bool HW>
+int32_t launch_basket_greeks_general(int A, const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds,
+                                     double* greeks, double* sums, hipStream_t stream) {
+  switch (A) {
+    case 1: return launch_basket_greeks_general_k<1, HW>(a, g, mode, lds, greeks, sums, stream);
+    case 2: return launch_basket_greeks_general_k<2, HW>(a, g, mode, lds, greeks, sums, stream);
+    case 3: return launch_basket_greeks_general_k<3, HW>(a, g, mode, lds, greeks, sums, stream);
+    case 4: return launch_basket_greeks_general_k<4, HW>(a, g, mode, lds, greeks, sums, stream);
+    case 5: return launch_basket_greeks_general_k<5, HW>(a, g, mode, lds, greeks, sums, stream);
+    case 6: return launch_basket_greeks_general_k<6, HW>(a, g, mode, lds, greeks, sums, stream);
+    case 7: return launch_basket_greeks_general_k<7, HW>(a, g, mode, lds, greeks, sums, stream);
+    case 8: return launch_basket_greeks_general_k<8, HW>(a, g, mode, lds, greeks, sums, stream);
+    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: n_assets must be in 1..8");
+  }
+}
+
 }  // namespace
 }  // namespace smc
 
@@ -2053,6 +2540,65 @@ const char* smc_basket_greeks_kernel(int32_t n_assets, int32_t timesteps, int64_
 
 int32_t smc_basket_greeks_cols(int32_t n_assets) {
   return n_assets < 1 || n_assets > kMaxAssets ? -1 : 8 * n_assets + 16;
+}
+
+int32_t smc_basket_greeks_general(const double* contracts_dev, const double* weights_dev, int64_t weights_stride,
+                                  const double* corr_dev, int64_t corr_stride, int64_t n_contracts, int32_t n_assets,
+                                  int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                                  int64_t ordinal0, int32_t math, int32_t normalization, double* greeks_dev,
+                                  double* sums_dev, void* stream) {
+  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: contracts_dev is NULL");
+  if (!greeks_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: greeks_dev is NULL");
+  if (n_assets < 1 || n_assets > kMaxAssets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: n_assets must be in 1..8");
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_basket_greeks_general: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: bad normalization");
+  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
+    return fail(SMC_ERR_INVALID_SHAPE,
+                "smc_basket_greeks_general: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
+  if (n_paths >= (int64_t{1} << 40))
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_greeks_general: n_paths too large (>= 2^40)");
+  if (weights_dev && weights_stride != 0 && weights_stride < n_assets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: weights_stride must be 0 or >= n_assets");
+  if (corr_dev && corr_stride != 0 && corr_stride < n_assets * (n_assets - 1) / 2)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_basket_greeks_general: corr_stride must be 0 or >= n_assets (n_assets - 1) / 2");
+  if (n_contracts == 0) return SMC_OK;
+  size_t lds = 0;
+  const int mode = basket_greeks_general_mode(n_assets, n_paths, math, normalization, &lds);
+  BasketArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.normalize = normalization != SMC_NORM_RAW;
+  // A = 1 has no correlation entry: nothing to read, whatever the caller passed
+  const BasketGeneralArgs g{weights_dev, weights_stride, n_assets > 1 ? corr_dev : nullptr, corr_stride};
+  return (math & SMC_MATH_HW)
+             ? launch_basket_greeks_general<true>(n_assets, a, g, mode, lds, greeks_dev, sums_dev, as_stream(stream))
+             : launch_basket_greeks_general<false>(n_assets, a, g, mode, lds, greeks_dev, sums_dev, as_stream(stream));
+}
+
+const char* smc_basket_greeks_general_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                             int32_t normalization) {
+  size_t lds = 0;
+  if (timesteps <= 0) return "unsupported";
+  switch (basket_greeks_general_mode(n_assets, n_paths, math, normalization, &lds)) {
+    case kBPriceRaw: return "basket_greeks_general_kernel(raw)";
+    case kBPriceLds: return "basket_greeks_general_kernel(lds)";
+    case kBPriceReplay: return "basket_greeks_general_kernel(replay)";
+    default: return "unsupported";
+  }
+}
+
+int32_t smc_basket_greeks_general_cols(int32_t n_assets) {
+  return n_assets < 1 || n_assets > kMaxAssets ? -1 : 2 * n_assets * n_assets + 6 * n_assets + 12;
 }
 
 #pragma GCC visibility pop
