@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general; smc_basket_greeks_general (with its _kernel and _cols queries) was added under 21 without a new number: the change is purely additive, no existing entry point moved, and the library ships together with the bindings that load it */
+#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general; smc_basket_greeks_general (with its _kernel and _cols queries) was added under 21 without a new number: the change is purely additive, no existing entry point moved, and the library ships together with the bindings that load it; smc_basket_price_paths (with its _kernel query) was added under 21 in the same way */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -459,7 +459,7 @@ const char* smc_gbm_price_paths_kernel(int32_t timesteps, int64_t n_paths, int32
  * (rho <= -1 / (A - 1)) gives NaN, and rho = 1 is only meaningful for A <= 2 (from A = 3 on the
  * Banachiewicz factorisation divides 0 by 0).  B below the CU count leaves CUs idle (a contract is not split
  * over workgroups).  Equal weights and equicorrelation only (caller weights and a general correlation matrix:
- * smc_basket_price_general, below); no path-dependent basket payoffs. */
+ * smc_basket_price_general, below; path-dependent basket payoffs: smc_basket_price_paths, below). */
 #define SMC_BASKET_PRICE_COLS 18
 int32_t smc_basket_price(const double* contracts_dev /*[B][3A+4]*/, int64_t n_contracts, int32_t n_assets,
                          int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
@@ -643,8 +643,8 @@ int32_t smc_basket_greeks_cols(int32_t n_assets);
  * Stream-ordered: no allocation, no synchronisation, capturable into a graph.  Nothing is validated on the
  * device, as elsewhere: a matrix that is not positive definite (the factor takes sqrt(max(s, 0)) and divides by
  * it) or a non-finite weight gives non-finite or meaningless rows; check on the host if the input is not trusted.
- * Out of scope: weights or a general correlation in the training targets; a float64 basket engine; path-dependent
- * basket payoffs.  This basket's Greeks and sensitivities to correlation entries: smc_basket_greeks_general, below. */
+ * Out of scope: weights or a general correlation in the training targets; a float64 basket engine.  Greeks and correlation
+ * sensitivities: smc_basket_greeks_general, below; Asian, barrier and lookback payoffs: smc_basket_price_paths, below. */
 int32_t smc_basket_price_general(const double* contracts_dev /*[B][3A+4]*/,
                                  const double* weights_dev /*rows of A, or NULL*/, int64_t weights_stride,
                                  const double* corr_dev /*rows of A(A-1)/2, or NULL*/, int64_t corr_stride,
@@ -749,6 +749,72 @@ const char* smc_basket_greeks_general_kernel(int32_t n_assets, int32_t timesteps
                                              int32_t normalization);
 /* Doubles per contract of greeks_dev: 2 A^2 + 6 A + 12; -1 for n_assets outside 1..8. */
 int32_t smc_basket_greeks_general_cols(int32_t n_assets);
+
+/* ---- path-dependent basket pricing (additive under ABI 21) -----------------------
+ * Asian, barrier and lookback options on the basket level, and worst-of barrier structures, for B contracts in ONE
+ * launch: smc_gbm_price_paths for the basket smc_basket_price_general prices.  The T monitoring dates are the T grid
+ * points of the simulation (X0 is not monitored); no row of the [A][T][P] block is ever stored.
+ * Taken unchanged from smc_basket_price_general: the contract rows ([B][3A+4]), the streams and the ordinal handling,
+ * weights_dev / weights_stride (NULL = f32(1.0 / A), stride 0 shares row 0, any sign), corr_dev / corr_stride (the
+ * packed strict lower triangle; NULL = the row's rho) and the factor, the step coefficients, the 512-lane workgroup
+ * per contract, 4 paths per lane, 2048-path chunks, validity for any n_paths >= 1, A in 1..8, K and df.
+ * Monitored values, for asset i and row t: xs_it = x_it s_it, rounded to f32.  s_it = 1 under SMC_NORM_RAW.  Under
+ * SMC_NORM_NORMALIZE s_it = F_it / f32(rowsum_it / f64(P)) with F_it = f32(X0_i) exp(f32(r - d_i) f32(tau_t)),
+ * tau_t = (t + 1) (T / timesteps) in f64 for t < timesteps - 1 and tau = T exactly for the last row, and rowsum_it in
+ * the order smc_basket_price_general takes tot_i: the lane's valid values left to right in f32 from 0, cast to f64 and
+ * added per lane over its chunks, the wave butterfly xor 32..1, waves 0..7.  So the last row's sum, scale and forward
+ * are that call's tot_i, s_i and F_i bit for bit, and terminal_sum_dev ([B][A] or NULL) is its output bit for bit.
+ * Per path, all in f32, every operation rounded (no fused multiply-add), rows t = 0 .. timesteps - 1 in order:
+ *   b_t = ((0 + w_0 xs_0t) + w_1 xs_1t) + ...      m_t = min_i xs_it  (unweighted, as the price call's mn)
+ *   avg = (((0 + b_0) + b_1) + ...) / f32(timesteps)      mxb = max_t b_t      mnb = min_t b_t
+ *   ko = any_t (b_t <= lower || b_t >= upper)      wko = any_t (m_t <= worst_lower)
+ * with (lower, upper, worst_lower) = f32 of barriers_dev[b][0..2]; barriers_dev NULL means (-inf, +inf, -inf).  The
+ * comparisons are plain ones: a side is switched off with -inf or +inf, not with 0 (a spread's level may be
+ * negative).  Payoffs are df max(. , 0), cast to f64 and added with their squares.  prices_dev [B][25]:
+ *    0 / 1  Asian basket put K - avg / call avg - K
+ *    2 / 3  knock-out basket put / call: 0 if ko, else K - b_last / b_last - K
+ *    4 / 5  lookback basket put K - mnb / call mxb - K
+ *    6 / 7  worst-of put / call knocked out on the worst asset: 0 if wko, else K - m_last / m_last - K
+ *    8 / 9  European basket put / call (smc_basket_price_general's columns 0 / 1 bit for bit)
+ *   10..19  the standard errors of columns 0..9 (the price call's formula; 0 at P = 1)
+ *   20 mean of avg    21 share of paths with ko    22 share with wko    23 mean of mxb    24 mean of mnb
+ * Knock-ins follow by difference: European minus knock-out for the basket columns, smc_basket_price_general's
+ * worst-of columns 4 / 5 minus 6 / 7 for the worst-of ones.  Without barriers columns 2, 3, 12, 13 are 8, 9, 18, 19,
+ * columns 6, 7, 16, 17 are the price call's 4, 5, 10, 11 and columns 21, 22 are 0, bit for bit; at timesteps = 1
+ * columns 0, 1, 4, 5 and their errors are 8, 9 and theirs and 20, 23, 24 are the price call's column 12.
+ * Each column's sum runs per lane over its chunks and paths in order, then the wave butterfly, then waves 0..7: the
+ * block is bit-identical run to run, under any split of the batch, with the ordinal on the host or the device.
+ * Passes.  RAW: one simulation.  NORMALIZE: the A * timesteps row sums are per-lane f64 accumulators in LDS
+ * ([R][512]), R rows at a time in sweeps of floor(R / A) whole dates, each sweep simulating from row 0 to its last
+ * row (a row's sum lies in one sweep, so sweep boundaries change no order); R is what fits in 144 KiB beside 2112
+ * bytes of scratch and the A * timesteps f32 scales; a final simulation takes the payoffs.  For A = 5..8 the 25 sums
+ * and the per-path state do not fit in registers beside the 4 A path values: the columns are then taken in three
+ * groups over three payoff simulations ({Asian, European, 20}, {knock-out, worst-of knock-out, 21, 22}, {lookback,
+ * 23, 24}); a sum belongs to one group and keeps its order.
+ * math: 0 or SMC_MATH_HW.  SMC_PRICE_REPLAY is accepted and changes nothing (there is no parked mode: A T P values
+ * do not fit in LDS); any other bit is rejected.
+ * Checks: smc_basket_price_general's, in its order and with its status codes (NULL contracts_dev, NULL prices_dev,
+ * n_assets, math, normalization: SMC_ERR_INVALID_ARGUMENT; n_contracts, timesteps, n_paths: SMC_ERR_INVALID_SHAPE;
+ * weights_stride, corr_stride: SMC_ERR_INVALID_ARGUMENT); then SMC_ERR_INVALID_SHAPE for a NORMALIZE run whose
+ * n_assets * timesteps scales do not fit the LDS table beside one date of accumulators; all before the empty batch
+ * (n_contracts = 0: SMC_OK, nothing touched) is accepted.
+ * Stream-ordered: no allocation, no synchronisation, no workspace, no atomics, capturable into a graph.  Nothing is
+ * validated on the device (NaN barriers never knock; lower >= upper knocks every path).
+ * Out of scope: Greeks of these payoffs; continuous-monitoring corrections; geometric averages; per-asset barrier
+ * levels; a float64 basket engine; weights or a general correlation in the training targets. */
+#define SMC_BASKET_PATH_COLS 25
+int32_t smc_basket_price_paths(const double* contracts_dev /*[B][3A+4]*/,
+                               const double* weights_dev /*rows of A, or NULL*/, int64_t weights_stride,
+                               const double* corr_dev /*rows of A(A-1)/2, or NULL*/, int64_t corr_stride,
+                               const double* barriers_dev /*[B][3] or NULL*/,
+                               int64_t n_contracts, int32_t n_assets, int32_t timesteps, int64_t n_paths,
+                               uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
+                               int32_t normalization, double* prices_dev /*[B][25]*/,
+                               double* terminal_sum_dev /*[B][A] or NULL*/, void* stream);
+/* "basket_path_kernel(raw)", "basket_path_kernel(replay)" or "unsupported" (a call smc_basket_price_paths
+ * rejects).  Static string, no device call. */
+const char* smc_basket_price_paths_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                          int32_t normalization);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,7 @@ PRICE_REPLAY = 0x800  # smc_gbm_price scheme flag: never park the terminal value
 PRICE_COLS = 8  # doubles per contract smc_gbm_price writes
 PATH_PRICE_COLS = 20  # doubles per contract smc_gbm_price_paths writes
 BASKET_PRICE_COLS = 18  # doubles per contract smc_basket_price writes
+BASKET_PATH_COLS = 25  # doubles per contract smc_basket_price_paths writes
 GREEKS_COLS = 26  # doubles per contract smc_gbm_greeks writes
 ABI_VERSION = 21
 
@@ -118,6 +119,9 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
                                            _c_vp, _c_i64, _c_i32, _c_i32, _c_vp, _c_vp, _c_vp]),
     "smc_basket_greeks_general_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i32]),
     "smc_basket_greeks_general_cols": (_c_i32, [_c_i32]),
+    "smc_basket_price_paths": (_c_i32, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i64,
+                                        _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp, _c_vp, _c_vp]),
+    "smc_basket_price_paths_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i32]),
 }
 
 # include/spectralmc_hip_testing.h: test-only entry points, inert unless SMC_ENABLE_TEST_HOOKS=1

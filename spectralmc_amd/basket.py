@@ -23,7 +23,9 @@ B contracts, no terminal buffer in memory; with ``weights=`` and / or ``correlat
 weights and full correlation matrix (``smc_basket_price_general``).  ``basket_greeks`` / ``BasketEngine.greeks``
 give the basket put's and call's per-asset deltas and vegas, rho, theta and correlation sensitivity the same way
 (``smc_basket_greeks``; with ``weights=`` and / or ``correlation=`` those of the weighted, general-correlation basket, the
-correlation sensitivity per pair: ``smc_basket_greeks_general``).
+correlation sensitivity per pair: ``smc_basket_greeks_general``).  ``basket_price_paths`` / ``BasketEngine.price_paths``
+price the path-dependent payoffs of that basket over the monitoring dates (Asian, knock-out, lookback, worst-of
+knock-out: ``smc_basket_price_paths``).
 """
 
 from __future__ import annotations
@@ -329,6 +331,119 @@ def basket_price(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 
                 norm, _lib.ptr(block), _lib.ptr(tsum), _lib.stream_handle()))
     return BasketPrices(**{name: block[:, col] for col, name in enumerate(PRICE_FIELDS)}, terminal_sum=tsum,
                         block=block)
+
+
+BASKET_PATH_FIELDS = ("asian_put", "asian_call", "knock_out_put", "knock_out_call", "lookback_put", "lookback_call",
+                      "worst_knock_out_put", "worst_knock_out_call", "european_put", "european_call",
+                      "asian_put_stderr", "asian_call_stderr", "knock_out_put_stderr", "knock_out_call_stderr",
+                      "lookback_put_stderr", "lookback_call_stderr", "worst_knock_out_put_stderr",
+                      "worst_knock_out_call_stderr", "european_put_stderr", "european_call_stderr", "mean_average",
+                      "knocked_share", "worst_knocked_share", "mean_max", "mean_min")
+
+
+@dataclass(frozen=True)
+class BasketPathPrices:
+    """``smc_basket_price_paths``'s block for B contracts: one [B] f64 device tensor per column (views of ``block``
+    [B, 25], in ``BASKET_PATH_FIELDS`` order) and the raw terminal sums ``terminal_sum`` [B, A].  Knock-ins follow by
+    difference: ``european_*`` minus ``knock_out_*``, and ``basket_price``'s ``worst_of_*`` minus
+    ``worst_knock_out_*``."""
+    asian_put: torch.Tensor
+    asian_call: torch.Tensor
+    knock_out_put: torch.Tensor
+    knock_out_call: torch.Tensor
+    lookback_put: torch.Tensor
+    lookback_call: torch.Tensor
+    worst_knock_out_put: torch.Tensor
+    worst_knock_out_call: torch.Tensor
+    european_put: torch.Tensor
+    european_call: torch.Tensor
+    asian_put_stderr: torch.Tensor
+    asian_call_stderr: torch.Tensor
+    knock_out_put_stderr: torch.Tensor
+    knock_out_call_stderr: torch.Tensor
+    lookback_put_stderr: torch.Tensor
+    lookback_call_stderr: torch.Tensor
+    worst_knock_out_put_stderr: torch.Tensor
+    worst_knock_out_call_stderr: torch.Tensor
+    european_put_stderr: torch.Tensor
+    european_call_stderr: torch.Tensor
+    mean_average: torch.Tensor
+    knocked_share: torch.Tensor
+    worst_knocked_share: torch.Tensor
+    mean_max: torch.Tensor
+    mean_min: torch.Tensor
+    terminal_sum: torch.Tensor
+    block: torch.Tensor
+
+
+def validate_basket_barriers(barriers: torch.Tensor | None) -> None:
+    """``basket_price_paths(validate=True)``'s checks of the barriers (they read the values): ValueError for a NaN
+    and for a row with ``lower >= upper``."""
+    if barriers is None:
+        return
+    if bool(torch.isnan(barriers).any()):
+        raise ValueError("barriers must not be NaN (switch a side off with -inf / +inf)")
+    if bool((barriers[:, 0] >= barriers[:, 1]).any()):
+        raise ValueError("barriers must have lower < upper")
+
+
+def basket_price_paths(contracts: torch.Tensor, cfg: BasketConfig, *, barriers: torch.Tensor | None = None,
+                       weights: torch.Tensor | None = None, correlation: torch.Tensor | None = None,
+                       ordinal0: int = 0, n_paths: int | None = None, validate: bool = False) -> BasketPathPrices:
+    """Monte-Carlo prices of the path-dependent basket payoffs of device contracts [B, 3A+4] f64 (Asian, knock-out
+    and lookback options on the weighted basket level, worst-of options knocked out on the worst asset, and the
+    European basket beside them) over the ``cfg.timesteps`` monitoring dates: one launch of
+    ``smc_basket_price_paths`` on the current stream, no host synchronisation.  ``cfg`` gives n_assets, timesteps,
+    mc_seed, normalize and math; ``n_paths`` (default ``cfg.total_paths``) may be any positive count.
+
+    ``barriers``: a contiguous float64 device tensor [B, 3] of (lower, upper, worst_lower) per contract: the basket
+    is knocked out at a date where its level is <= lower or >= upper, the worst-of payoffs where the lowest scaled
+    asset value is <= worst_lower.  A side is switched off with -inf / +inf (a spread's level may be negative, so 0
+    is a level like any other); None switches all three off.  ``weights`` and ``correlation`` as ``basket_price``'s
+    (None: 1 / A and the rows' rho).  ``validate=True`` checks the values first (``validate_basket_inputs``, and
+    ``validate_basket_barriers``: no NaN, lower < upper) and is the only path that synchronises."""
+    if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
+            not contracts.is_contiguous():
+        raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
+    P = cfg.total_paths if n_paths is None else int(n_paths)
+    if P <= 0:
+        raise ValueError(f"n_paths must be positive, got {n_paths}")
+    B, A = contracts.shape[0], cfg.n_assets
+    if barriers is not None and (not isinstance(barriers, torch.Tensor) or barriers.dtype != torch.float64 or
+                                 not barriers.is_contiguous() or tuple(barriers.shape) != (B, 3)):
+        raise ValueError(f"barriers must be a contiguous float64 tensor of shape ({B}, 3)")
+    w_stride = c_stride = 0
+    packed = True
+    if weights is not None:
+        weights, w_stride = _general_weights(weights, B, A)
+    if correlation is not None:
+        correlation, c_stride, packed = _general_correlation(correlation, B, A)
+    given = (("barriers", barriers), ("weights", weights), ("correlation", correlation))
+    for name, t in given:
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
+    _lib.require_device()
+    if not contracts.is_cuda:
+        raise ValueError("contracts must be a device tensor")
+    for name, t in given:
+        if t is not None and t.device != contracts.device:
+            raise ValueError(f"{name} must be on the contracts' device")
+    if validate:
+        validate_basket_inputs(weights, correlation, A)
+        validate_basket_barriers(barriers)
+    block = torch.empty((B, _lib.BASKET_PATH_COLS), dtype=torch.float64, device=contracts.device)
+    tsum = torch.empty((B, A), dtype=torch.float64, device=contracts.device)
+    if B > 0:
+        tri = correlation if packed else pack_correlation(correlation)
+        if tri is not None and tri.numel() == 0:  # A = 1: no entry to read
+            tri = None
+        _lib.check(_lib.lib().smc_basket_price_paths(
+            _lib.ptr(contracts), _lib.ptr(weights), w_stride, _lib.ptr(tri), c_stride, _lib.ptr(barriers), B, A,
+            cfg.timesteps, P, cfg.mc_seed, None, ordinal0, _lib.MATH_HW if cfg.math == "hw" else 0,
+            _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW, _lib.ptr(block), _lib.ptr(tsum),
+            _lib.stream_handle()))
+    return BasketPathPrices(**{name: block[:, col] for col, name in enumerate(BASKET_PATH_FIELDS)}, terminal_sum=tsum,
+                            block=block)
 
 
 def basket_greeks_fields(n_assets: int) -> tuple[str, ...]:
@@ -648,6 +763,16 @@ class BasketEngine:
                              n_paths=n_paths, weights=weights, correlation=correlation, validate=validate)
 
 
+    def price_paths(self, contracts: torch.Tensor | None = None, *, barriers: torch.Tensor | None = None,
+                    weights: torch.Tensor | None = None, correlation: torch.Tensor | None = None, ordinal0: int = 0,
+                    n_paths: int | None = None, validate: bool = False) -> BasketPathPrices:
+        """Path-dependent Monte-Carlo prices (``basket_price_paths``) with the engine's configuration, by default of
+        the contracts of the last enqueued step.  The other arguments as ``basket_price_paths``'s."""
+        return basket_price_paths(self.buffers.contracts if contracts is None else contracts, self.cfg,
+                                  barriers=barriers, weights=weights, correlation=correlation, ordinal0=ordinal0,
+                                  n_paths=n_paths, validate=validate)
+
+
 def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) -> None:
     """Make ``pricer`` train on basket contracts: its training sessions build a ``BasketEngine``
     instead of the single-asset engine.  The pricer's CVNN must take ``cfg.dim`` inputs."""
@@ -658,7 +783,7 @@ def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) ->
     pricer.mc_engine_factory = factory
 
 
-__all__ = ["BasketConfig", "BasketEngine", "BasketGeneralGreeks", "BasketGreeks", "BasketPrices", "basket_fields",
-           "basket_general_greeks_fields", "basket_greeks", "basket_greeks_fields", "basket_price", "basket_targets",
-           "default_basket_bounds", "pack_correlation", "unpack_correlation", "use_basket_engine",
-           "validate_basket_inputs", "MAX_ASSETS"]
+__all__ = ["BASKET_PATH_FIELDS", "BasketConfig", "BasketEngine", "BasketGeneralGreeks", "BasketGreeks", "BasketPathPrices",
+           "BasketPrices", "basket_fields", "basket_general_greeks_fields", "basket_greeks", "basket_greeks_fields",
+           "basket_price", "basket_price_paths", "basket_targets", "default_basket_bounds", "pack_correlation",
+           "unpack_correlation", "use_basket_engine", "validate_basket_barriers", "validate_basket_inputs", "MAX_ASSETS"]

@@ -338,9 +338,17 @@ constexpr size_t kBPriceParkBytes = SMC_PRICE_PARK_BYTES;
 
 // The lane's 4 paths of all A assets of one chunk from x0 through the T steps: basket_kernel's path loop
 // without its row stores (the same draws and packed f32 ops in the same order).
-template <int A, bool HW>
+// hook (basket_path_kernel): called as hook(x, t) after the step that makes row t, with the lane's 4 values of
+// every asset; the default does nothing and leaves the callers' code as it was.
+struct NoBasketRowHook {
+  template <typename X>
+  __device__ __forceinline__ void operator()(const X&, int) const {}
+};
+
+template <int A, bool HW, typename Hook = NoBasketRowHook>
 __device__ __forceinline__ void basket_lane_paths(PathStream& s, const float (&ca)[A], const float (&x0)[A],
-                                                  const float (&Lb)[A][A], int T, float (&x)[A][kBPaths]) {
+                                                  const float (&Lb)[A][A], int T, float (&x)[A][kBPaths],
+                                                  Hook&& hook = Hook()) {
   typedef float f2 __attribute__((ext_vector_type(2)));
 #pragma unroll
   for (int i = 0; i < A; ++i)
@@ -367,6 +375,7 @@ __device__ __forceinline__ void basket_lane_paths(PathStream& s, const float (&c
         x[i][j + 1] = xv.y;
       }
     }
+    hook(x, t);
   }
 }
 
@@ -764,6 +773,296 @@ __global__ __launch_bounds__(kBThreads) void basket_general_kernel(BasketArgs a,
   }
 }
 
+template <int... I, typename F>
+__device__ __forceinline__ void basket_static_for(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+
+// ---- path-dependent basket pricing: basket_path_kernel (smc_basket_price_paths) ---------------------
+// basket_general_kernel's front end (contract rows, streams, weights, cholesky_general, step coefficients, the
+// 512-lane workgroup per contract, 4 paths per lane and 2048-path chunk, validity for any P >= 1) with
+// path_price_kernel's per-row hook on basket_lane_paths: every monitoring date t of the [A][T][P] block the
+// training call would store is seen in registers as xs_it = x_it s_it (s = 1 under RAW), and gives the basket
+// level b_t = ((0 + w_0 xs_0t) + w_1 xs_1t) + ... and the worst level m_t = min_i xs_it.  Each path keeps the
+// running sum, maximum and minimum of b_t and two knocked flags (b_t <= lower || b_t >= upper; m_t <= worst_lower).
+// From those come ten payoffs per path (Asian, knock-out, lookback, worst-of knock-out, European; put and call) and
+// kBPathSums f64 sums per contract: the payoffs, their squares, the average, the two knocked counts, the maximum and
+// the minimum.  There is no parked mode: A T P values do not fit in LDS.
+//   RAW        one simulation per column group; the terminal sums ride along with the first one as per-lane f64
+//              accumulators in dynamic LDS ([A][512], lane tid touches column tid only: no registers beside the
+//              payoff sums).
+//   NORMALIZE  first the A T row sums in basket_general_kernel's tot_i order (the lane's valid values left to right
+//              in f32 from 0, then f64 per lane over its chunks, butterfly, waves 0..7): the per-lane accumulators
+//              of R = dates * A rows live in dynamic LDS ([R][512] doubles), and the T dates are covered in sweeps
+//              of `dates` whole time rows, each re-simulating from row 0 to its last row; a row's sum lies in one
+//              sweep, so a sweep boundary changes no order.  The A T scales stay in LDS as f32 ([T][A]); the
+//              payoff simulations re-create the same streams and apply them.
+// Column groups: 25 f64 sums and 14 registers of per-path state fit beside the 4 A path values for A <= 4 (one
+// payoff simulation).  From A = 5 on the columns are taken in three groups over three simulations: {Asian,
+// European}, {knock-out, worst-of knock-out}, {lookback}; a sum belongs to one group and keeps its order, so the
+// European columns stay the price call's bit for bit.
+constexpr int kBPathSums = 25;  // 10 payoffs, their squares, avg, count(ko), count(wko), mxb, mnb
+// scratch at the head of the dynamic LDS: payoff-sum partials [kBWaves][kBPathSums] and the Cholesky factor [8][8]
+// (f64; 2112 B)
+constexpr int kBPathHead = kBWaves * kBPathSums + kMaxAssets * kMaxAssets;
+constexpr size_t kBPathScratch = kBPathHead * sizeof(double);
+constexpr size_t kBPathAccRow = kBThreads * sizeof(double);  // one row of per-lane row-sum accumulators
+constexpr size_t kBPathLdsBytes = 144 * 1024;                // dynamic LDS a workgroup may take
+constexpr int basket_path_groups(int A) { return A <= 4 ? 1 : 3; }
+// payoff family of a sum: 0 Asian, 1 knock-out, 2 lookback, 3 worst-of knock-out, 4 European
+constexpr int basket_path_family(int sum) {
+  return sum < 20 ? (sum % 10) / 2 : (sum == 20 ? 0 : (sum == 21 ? 1 : (sum == 22 ? 3 : 2)));
+}
+constexpr bool basket_path_in_group(int A, int group, int sum) {
+  if (basket_path_groups(A) == 1) return true;
+  const int f = basket_path_family(sum);
+  return group == 0 ? (f == 0 || f == 4) : (group == 1 ? (f == 1 || f == 3) : f == 2);
+}
+
+template <int A, bool HW, bool NORMALIZE>
+__global__ __launch_bounds__(kBThreads) void basket_path_kernel(BasketArgs a, BasketGeneralArgs g,
+                                                                const double* __restrict__ barriers,
+                                                                double* __restrict__ prices, int sweep_dates) {
+  constexpr int NG = basket_path_groups(A);
+  // kBPathHead doubles of scratch; NORMALIZE: then the A T scales (f32, padded to 8 B); then the accumulator rows
+  // ([sweep_dates * A][512] under NORMALIZE, [A][512] under RAW)
+  extern __shared__ double lds[];
+  double* Ld = lds + kBWaves * kBPathSums;  // [8][8]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  float* scales = reinterpret_cast<float*>(lds + kBPathHead);  // [T][A]
+  double* acc = lds + kBPathHead + (NORMALIZE ? (static_cast<size_t>(A) * T * sizeof(float) + 7) / 8 : 0);
+
+  const double* c = a.contracts + b * (3 * A + 4);
+  const double Tm = c[1], r = c[2], rho = c[3];
+  if (tid == 0) cholesky_general(A, rho, g.corr ? g.corr + b * g.corr_stride : nullptr, Ld);
+  __syncthreads();
+  // per-asset log2-unit coefficients, as basket_kernel
+  const double dt = Tm / static_cast<double>(T);
+  const double sq = sqrt(dt);
+  constexpr double zscale = HW ? PathStream::kNormalScale<true> : 1.0;
+  float ca[A], x0[A], Lb[A][A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double drift = r - d - 0.5 * v * v;
+    ca[i] = static_cast<float>(drift * dt * kBLog2e);
+    const double bi = v * sq * kBLog2e * zscale;
+    x0[i] = static_cast<float>(c[4 + i]);
+#pragma unroll
+    for (int k = 0; k < A; ++k) Lb[i][k] = k <= i ? static_cast<float>(bi * Ld[i * kMaxAssets + k]) : 0.0f;
+  }
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+
+  auto uniform = [](float f) {  // the same for every lane: kept in a scalar register
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, f)));
+  };
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = P - chunk - kBPaths * static_cast<int64_t>(tid);
+    return static_cast<int>(left <= 0 ? 0 : (left >= kBPaths ? kBPaths : left));
+  };
+  // the lane's valid values of one asset and row, left to right in f32 from 0, onto its own f64 accumulator
+  auto add_row = [&](double* slot, const float(&xr)[kBPaths], int nvalid) {
+    float p = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kBPaths; ++j) p += j < nvalid ? xr[j] : 0.0f;
+    *slot += static_cast<double>(p);
+  };
+  // rows [0, nrows) of acc: wave butterfly into lane 0's own slot; after the barrier thread q totals waves 0..7
+  auto reduce_rows = [&](int nrows) {
+    for (int q = 0; q < nrows; ++q) {
+      const double w = bwave_sum(acc[q * kBThreads + tid]);
+      if (lane == 0) acc[q * kBThreads + tid] = w;
+    }
+    __syncthreads();
+  };
+  auto row_total = [&](int q) {
+    double sum = 0.0;
+    for (int w = 0; w < kBWaves; ++w) sum += acc[q * kBThreads + w * 64];
+    return sum;
+  };
+
+  if constexpr (NORMALIZE) {
+    for (int t0 = 0; t0 < T; t0 += sweep_dates) {
+      const int nd = T - t0 < sweep_dates ? T - t0 : sweep_dates;
+      const int nrows = nd * A;  // <= the rows the host sized acc for
+      for (int q = 0; q < nrows; ++q) acc[q * kBThreads + tid] = 0.0;
+      for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+        const int nvalid = valid_paths(chunk);
+        if (nvalid > 0) {
+          PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+          float x[A][kBPaths];
+          basket_lane_paths<A, HW>(s, ca, x0, Lb, t0 + nd, x, [&](const float(&xr)[A][kBPaths], int t) {
+            if (t >= t0) {  // t < t0 + nd: date t - t0 of this sweep, the lane's own column
+              double* row = acc + static_cast<size_t>(t - t0) * A * kBThreads + tid;
+#pragma unroll
+              for (int i = 0; i < A; ++i) add_row(row + i * kBThreads, xr[i], nvalid);
+            }
+          });
+        }
+      }
+      reduce_rows(nrows);
+      if (tid < nrows) {
+        const double sum = row_total(tid);
+        const int idx = t0 * A + tid;  // t * A + i
+        scales[idx] = static_cast<float>(sum / static_cast<double>(P));  // the row mean, for now
+        if (a.terminal_sum && idx >= (T - 1) * A) a.terminal_sum[b * A + (idx - (T - 1) * A)] = sum;
+      }
+      __syncthreads();  // the accumulators are free for the next sweep
+    }
+    for (int idx = tid; idx < A * T; idx += kBThreads) {
+      const int t = idx / A, i = idx - t * A;
+      const double tau = t == T - 1 ? Tm : static_cast<double>(t + 1) * dt;
+      const float F = static_cast<float>(c[4 + i]) * math::exp_any(static_cast<float>(r - c[4 + A + i]) * static_cast<float>(tau));
+      scales[idx] = F / scales[idx];
+    }
+    __syncthreads();
+  }
+
+  // payoff constants (basket_general_kernel's), the weights and the barriers
+  const float Tf = static_cast<float>(Tm);
+  const float df = math::exp_any(static_cast<float>(-r) * Tf);
+  const float Kf = static_cast<float>(c[0]);
+  const float steps = static_cast<float>(T);
+  float wt[A];
+#pragma unroll
+  for (int i = 0; i < A; ++i)
+    wt[i] = uniform(g.weights ? static_cast<float>(g.weights[b * g.weights_stride + i]) : static_cast<float>(1.0 / A));
+  const float inf = __builtin_huge_valf();
+  const float lower = uniform(barriers ? static_cast<float>(barriers[3 * b]) : -inf);
+  const float upper = uniform(barriers ? static_cast<float>(barriers[3 * b + 1]) : inf);
+  const float wlower = uniform(barriers ? static_cast<float>(barriers[3 * b + 2]) : -inf);
+  auto pay = [&](float diff) { return static_cast<double>(df * (diff > 0.0f ? diff : 0.0f)); };
+  // basket and worst level of path j at row t
+  auto level = [&](const float(&xr)[A][kBPaths], const float(&sc)[A], int j, float& bt, float& mt) {
+    bt = 0.0f;
+    mt = 0.0f;
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+      const float xs = NORMALIZE ? xr[i][j] * sc[i] : xr[i][j];
+      bt = bt + wt[i] * xs;
+      mt = i == 0 || xs < mt ? xs : mt;
+    }
+  };
+  auto row_scales = [&](int t, float(&sc)[A]) {
+#pragma unroll
+    for (int i = 0; i < A; ++i) sc[i] = NORMALIZE ? scales[t * A + i] : 1.0f;
+  };
+
+  basket_static_for(std::make_integer_sequence<int, NG>{}, [&](auto tag) {
+    constexpr int G = decltype(tag)::value;
+    constexpr bool ASIAN = basket_path_in_group(A, G, 0), KO = basket_path_in_group(A, G, 2),
+                   LOOK = basket_path_in_group(A, G, 4), WORST = basket_path_in_group(A, G, 6);
+    constexpr bool TERMINAL = !NORMALIZE && G == 0;  // RAW: the terminal sums ride along with the first group
+    double v[kBPathSums];
+#pragma unroll
+    for (int k = 0; k < kBPathSums; ++k) v[k] = 0.0;
+    if constexpr (TERMINAL)
+      for (int i = 0; i < A; ++i) acc[i * kBThreads + tid] = 0.0;
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float sa[kBPaths], mxb[kBPaths], mnb[kBPaths];
+        unsigned ko = 0, wko = 0;
+#pragma unroll
+        for (int j = 0; j < kBPaths; ++j) {
+          sa[j] = 0.0f;
+          mxb[j] = -inf;
+          mnb[j] = inf;
+        }
+        PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+        float x[A][kBPaths];
+        basket_lane_paths<A, HW>(s, ca, x0, Lb, T, x, [&](const float(&xr)[A][kBPaths], int t) {
+          float sc[A];
+          row_scales(t, sc);
+#pragma unroll
+          for (int j = 0; j < kBPaths; ++j) {
+            float bt, mt;
+            level(xr, sc, j, bt, mt);
+            if constexpr (ASIAN) sa[j] = sa[j] + bt;
+            if constexpr (LOOK) {
+              mxb[j] = bt > mxb[j] ? bt : mxb[j];
+              mnb[j] = bt < mnb[j] ? bt : mnb[j];
+            }
+            if constexpr (KO) ko |= (bt <= lower || bt >= upper) ? (1u << j) : 0u;
+            if constexpr (WORST) wko |= mt <= wlower ? (1u << j) : 0u;
+          }
+        });
+        if constexpr (TERMINAL) {
+#pragma unroll
+          for (int i = 0; i < A; ++i) add_row(acc + i * kBThreads + tid, x[i], nvalid);
+        }
+        float sc[A];
+        row_scales(T - 1, sc);
+#pragma unroll
+        for (int j = 0; j < kBPaths; ++j) {
+          if (j < nvalid) {
+            float bl, ml;  // the hook's values of row T - 1
+            level(x, sc, j, bl, ml);
+            const float avg = sa[j] / steps;
+            const bool kb = (ko >> j) & 1u, kw = (wko >> j) & 1u;
+            const double put = pay(Kf - bl), call = pay(bl - Kf), wput = pay(Kf - ml), wcall = pay(ml - Kf);
+            const double p[10] = {pay(Kf - avg),    pay(avg - Kf),    kb ? 0.0 : put,  kb ? 0.0 : call, pay(Kf - mnb[j]),
+                                  pay(mxb[j] - Kf), kw ? 0.0 : wput, kw ? 0.0 : wcall, put,             call};
+#pragma unroll
+            for (int k = 0; k < 10; ++k) {
+              if constexpr (NG == 1) {
+                v[k] += p[k];
+                v[10 + k] += p[k] * p[k];
+              } else if (basket_path_in_group(A, G, k)) {
+                v[k] += p[k];
+                v[10 + k] += p[k] * p[k];
+              }
+            }
+            if constexpr (ASIAN) v[20] += static_cast<double>(avg);
+            if constexpr (KO) v[21] += kb ? 1.0 : 0.0;
+            if constexpr (WORST) v[22] += kw ? 1.0 : 0.0;
+            if constexpr (LOOK) {
+              v[23] += static_cast<double>(mxb[j]);
+              v[24] += static_cast<double>(mnb[j]);
+            }
+          }
+        }
+      }
+    }
+    // the group's sums: wave butterfly into its own slots of the partials (the groups' slots are disjoint)
+#pragma unroll
+    for (int k = 0; k < kBPathSums; ++k) {
+      if (basket_path_in_group(A, G, k)) {
+        const double w = bwave_sum(v[k]);
+        if (lane == 0) lds[wave * kBPathSums + k] = w;
+      }
+    }
+    if constexpr (TERMINAL) {
+      reduce_rows(A);
+      if (tid < A && a.terminal_sum) a.terminal_sum[b * A + tid] = row_total(tid);
+    }
+  });
+  __syncthreads();
+  // waves 0..7, sum k totalled by thread k alone (path_price_kernel's way)
+  auto total = [&](int k) {
+    double t2 = 0.0;
+    for (int w = 0; w < kBWaves; ++w) t2 += lds[w * kBPathSums + k];
+    return t2;
+  };
+  const double n = static_cast<double>(P);
+  double* out = prices + b * SMC_BASKET_PATH_COLS;
+  if (tid < 10) {  // a payoff's mean and standard error
+    const double m = total(tid) / n;
+    double se = 0.0;
+    if (P > 1) {
+      const double var = total(10 + tid) - n * m * m;
+      se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+    }
+    out[tid] = m;
+    out[10 + tid] = se;
+  } else if (tid >= 20 && tid < kBPathSums) {
+    out[tid] = total(tid) / n;
+  }
+}
+
 // ---- batched basket Greeks: basket_greeks_kernel (smc_basket_greeks) -----------------------------
 // basket_price_kernel's geometry, streams, chunk / validity handling, modes and sum orders (restated, not
 // shared: basket_price_kernel's registers stay as they are; the path loop is basket_lane_paths, which only the
@@ -813,11 +1112,6 @@ __device__ __forceinline__ float basket_greeks_log(float x, float x0) {
   const float q = x / x0;
   if constexpr (HW) return math::hw_log(q);
   else return math::log_pos(q);
-}
-
-template <int... I, typename F>
-__device__ __forceinline__ void basket_static_for(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
 }
 
 template <int A, bool HW, int MODE>
@@ -2302,6 +2596,55 @@ int32_t launch_basket_greeks_general(int A, const BasketArgs& a, const BasketGen
   }
 }
 
+// basket_path_kernel's plan for a shape (host only, no HIP call): 0 one RAW simulation per column group, 1 the
+// NORMALIZE replay, -1 not a call it takes, -2 more scales (A T) than LDS holds beside one date of accumulators.
+// *dates is the number of whole time rows per sweep (NORMALIZE), *lds the dynamic LDS.
+int basket_path_plan(int A, int32_t T, int64_t P, int32_t math, int32_t normalization, size_t* lds, int* dates) {
+  if (A < 1 || A > kMaxAssets || T <= 0 || P <= 0 || P >= (int64_t{1} << 40)) return -1;
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
+  *dates = 0;
+  *lds = kBPathScratch + static_cast<size_t>(A) * kBPathAccRow;
+  if (normalization == SMC_NORM_RAW) return 0;
+  const size_t head = kBPathScratch + ((static_cast<size_t>(A) * static_cast<size_t>(T) * sizeof(float) + 7) & ~size_t{7});
+  if (head + static_cast<size_t>(A) * kBPathAccRow > kBPathLdsBytes) return -2;
+  const size_t fit = (kBPathLdsBytes - head) / kBPathAccRow / static_cast<size_t>(A);  // >= 1
+  *dates = static_cast<int>(static_cast<size_t>(T) < fit ? static_cast<size_t>(T) : fit);
+  *lds = head + static_cast<size_t>(*dates) * A * kBPathAccRow;
+  return 1;
+}
+
+template <int A, bool HW>
+int32_t launch_basket_path_k(const BasketArgs& a, const BasketGeneralArgs& g, const double* barriers, size_t lds,
+                             int dates, double* prices, hipStream_t stream) {
+  auto kernel = a.normalize ? basket_path_kernel<A, HW, true> : basket_path_kernel<A, HW, false>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "basket_path_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, g, barriers,
+         prices, dates);
+  return check_launch("basket_path_kernel");
+}
+
+template <bool HW>
+int32_t launch_basket_path(int A, const BasketArgs& a, const BasketGeneralArgs& g, const double* barriers, size_t lds,
+                           int dates, double* prices, hipStream_t stream) {
+  switch (A) {
+    case 1: return launch_basket_path_k<1, HW>(a, g, barriers, lds, dates, prices, stream);
+    case 2: return launch_basket_path_k<2, HW>(a, g, barriers, lds, dates, prices, stream);
+    case 3: return launch_basket_path_k<3, HW>(a, g, barriers, lds, dates, prices, stream);
+    case 4: return launch_basket_path_k<4, HW>(a, g, barriers, lds, dates, prices, stream);
+    case 5: return launch_basket_path_k<5, HW>(a, g, barriers, lds, dates, prices, stream);
+    case 6: return launch_basket_path_k<6, HW>(a, g, barriers, lds, dates, prices, stream);
+    case 7: return launch_basket_path_k<7, HW>(a, g, barriers, lds, dates, prices, stream);
+    case 8: return launch_basket_path_k<8, HW>(a, g, barriers, lds, dates, prices, stream);
+    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: n_assets must be in 1..8");
+  }
+}
+
 }  // namespace
 }  // namespace smc
 
@@ -2599,6 +2942,64 @@ const char* smc_basket_greeks_general_kernel(int32_t n_assets, int32_t timesteps
 
 int32_t smc_basket_greeks_general_cols(int32_t n_assets) {
   return n_assets < 1 || n_assets > kMaxAssets ? -1 : 2 * n_assets * n_assets + 6 * n_assets + 12;
+}
+
+int32_t smc_basket_price_paths(const double* contracts_dev, const double* weights_dev, int64_t weights_stride,
+                               const double* corr_dev, int64_t corr_stride, const double* barriers_dev,
+                               int64_t n_contracts, int32_t n_assets, int32_t timesteps, int64_t n_paths,
+                               uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
+                               int32_t normalization, double* prices_dev, double* terminal_sum_dev, void* stream) {
+  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: contracts_dev is NULL");
+  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: prices_dev is NULL");
+  if (n_assets < 1 || n_assets > kMaxAssets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: n_assets must be in 1..8");
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_basket_price_paths: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: bad normalization");
+  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
+    return fail(SMC_ERR_INVALID_SHAPE,
+                "smc_basket_price_paths: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
+  if (n_paths >= (int64_t{1} << 40))
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price_paths: n_paths too large (>= 2^40)");
+  if (weights_dev && weights_stride != 0 && weights_stride < n_assets)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: weights_stride must be 0 or >= n_assets");
+  if (corr_dev && corr_stride != 0 && corr_stride < n_assets * (n_assets - 1) / 2)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_basket_price_paths: corr_stride must be 0 or >= n_assets (n_assets - 1) / 2");
+  size_t lds = 0;
+  int dates = 0;
+  if (basket_path_plan(n_assets, timesteps, n_paths, math, normalization, &lds, &dates) < 0)
+    return fail(SMC_ERR_INVALID_SHAPE,
+                "smc_basket_price_paths: n_assets * timesteps scales do not fit the LDS table (SMC_NORM_NORMALIZE)");
+  if (n_contracts == 0) return SMC_OK;
+  BasketArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.normalize = normalization != SMC_NORM_RAW;
+  a.terminal_sum = terminal_sum_dev;
+  // A = 1 has no correlation entry: nothing to read, whatever the caller passed
+  const BasketGeneralArgs g{weights_dev, weights_stride, n_assets > 1 ? corr_dev : nullptr, corr_stride};
+  return (math & SMC_MATH_HW)
+             ? launch_basket_path<true>(n_assets, a, g, barriers_dev, lds, dates, prices_dev, as_stream(stream))
+             : launch_basket_path<false>(n_assets, a, g, barriers_dev, lds, dates, prices_dev, as_stream(stream));
+}
+
+const char* smc_basket_price_paths_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                          int32_t normalization) {
+  size_t lds = 0;
+  int dates = 0;
+  switch (basket_path_plan(n_assets, timesteps, n_paths, math, normalization, &lds, &dates)) {
+    case 0: return "basket_path_kernel(raw)";
+    case 1: return "basket_path_kernel(replay)";
+    default: return "unsupported";
+  }
 }
 
 #pragma GCC visibility pop
