@@ -273,6 +273,68 @@ def validate_basket_inputs(weights: torch.Tensor | None, correlation: torch.Tens
         raise ValueError("correlation must be positive definite")
 
 
+@dataclass(frozen=True)
+class _BatchedCall:
+    """What ``basket_price``, ``basket_greeks`` and ``basket_price_paths`` hand to the library after the shared
+    checks: the shape, the prepared ``weights`` and packed correlation rows ``tri`` with their strides (None and 0
+    where not given) and the ``math`` / ``norm`` flags."""
+    B: int
+    A: int
+    P: int
+    general: bool
+    weights: torch.Tensor | None
+    w_stride: int
+    tri: torch.Tensor | None
+    c_stride: int
+    math: int
+    norm: int
+
+
+def _batched_call(contracts: torch.Tensor, cfg: BasketConfig, n_paths: int | None, weights: torch.Tensor | None,
+                  correlation: torch.Tensor | None, validate: bool, *, replay: bool = False,
+                  barriers: torch.Tensor | None = None) -> _BatchedCall:
+    """The checks the batched calls share, in their order: the tensors' shapes before the device is asked for, their
+    placement after it, then ``validate``'s look at the values."""
+    if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
+            not contracts.is_contiguous():
+        raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
+    P = cfg.total_paths if n_paths is None else int(n_paths)
+    if P <= 0:
+        raise ValueError(f"n_paths must be positive, got {n_paths}")
+    B, A = contracts.shape[0], cfg.n_assets
+    if barriers is not None and (not isinstance(barriers, torch.Tensor) or barriers.dtype != torch.float64 or
+                                 not barriers.is_contiguous() or tuple(barriers.shape) != (B, 3)):
+        raise ValueError(f"barriers must be a contiguous float64 tensor of shape ({B}, 3)")
+    general = weights is not None or correlation is not None
+    w_stride = c_stride = 0
+    packed = True
+    if weights is not None:
+        weights, w_stride = _general_weights(weights, B, A)
+    if correlation is not None:
+        correlation, c_stride, packed = _general_correlation(correlation, B, A)
+    given = (("barriers", barriers), ("weights", weights), ("correlation", correlation))
+    for name, t in given:
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
+    _lib.require_device()
+    if not contracts.is_cuda:
+        raise ValueError("contracts must be a device tensor")
+    for name, t in given:
+        if t is not None and t.device != contracts.device:
+            raise ValueError(f"{name} must be on the contracts' device")
+    if validate:
+        validate_basket_inputs(weights, correlation, A)
+        validate_basket_barriers(barriers)
+    tri = None
+    if B > 0 and correlation is not None:
+        tri = correlation if packed else pack_correlation(correlation)
+        if tri.numel() == 0:  # A = 1: no entry to read
+            tri = None
+    return _BatchedCall(B=B, A=A, P=P, general=general, weights=weights, w_stride=w_stride, tri=tri, c_stride=c_stride,
+                        math=(_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0),
+                        norm=_lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW)
+
+
 def basket_price(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 0, n_paths: int | None = None,
                  replay: bool = False, weights: torch.Tensor | None = None, correlation: torch.Tensor | None = None,
                  validate: bool = False) -> BasketPrices:
@@ -288,47 +350,18 @@ def basket_price(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int = 
     equicorrelation ``rho``, otherwise that column is ignored.  The values are not checked on the device
     (an indefinite matrix gives non-finite or meaningless rows); ``validate=True`` checks them here first
     (``validate_basket_inputs``) and is the only path that synchronises."""
-    if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
-            not contracts.is_contiguous():
-        raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
-    P = cfg.total_paths if n_paths is None else int(n_paths)
-    if P <= 0:
-        raise ValueError(f"n_paths must be positive, got {n_paths}")
-    B, A = contracts.shape[0], cfg.n_assets
-    general = weights is not None or correlation is not None
-    w_stride = c_stride = 0
-    packed = True
-    if weights is not None:
-        weights, w_stride = _general_weights(weights, B, A)
-    if correlation is not None:
-        correlation, c_stride, packed = _general_correlation(correlation, B, A)
-    for name, t in (("weights", weights), ("correlation", correlation)):
-        if t is not None and not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor")
-    _lib.require_device()
-    if not contracts.is_cuda:
-        raise ValueError("contracts must be a device tensor")
-    for name, t in (("weights", weights), ("correlation", correlation)):
-        if t is not None and t.device != contracts.device:
-            raise ValueError(f"{name} must be on the contracts' device")
-    if validate:
-        validate_basket_inputs(weights, correlation, A)
+    c = _batched_call(contracts, cfg, n_paths, weights, correlation, validate, replay=replay)
+    B, A = c.B, c.A
     block = torch.empty((B, _lib.BASKET_PRICE_COLS), dtype=torch.float64, device=contracts.device)
-    tsum = torch.empty((B, cfg.n_assets), dtype=torch.float64, device=contracts.device)
-    if B > 0:
-        math = (_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0)
-        norm = _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW
-        if general:
-            tri = correlation if packed else pack_correlation(correlation)
-            if tri is not None and tri.numel() == 0:  # A = 1: no entry to read
-                tri = None
-            _lib.check(_lib.lib().smc_basket_price_general(
-                _lib.ptr(contracts), _lib.ptr(weights), w_stride, _lib.ptr(tri), c_stride, B, A, cfg.timesteps, P,
-                cfg.mc_seed, None, ordinal0, math, norm, _lib.ptr(block), _lib.ptr(tsum), _lib.stream_handle()))
-        else:
-            _lib.check(_lib.lib().smc_basket_price(
-                _lib.ptr(contracts), B, cfg.n_assets, cfg.timesteps, P, cfg.mc_seed, None, ordinal0, math,
-                norm, _lib.ptr(block), _lib.ptr(tsum), _lib.stream_handle()))
+    tsum = torch.empty((B, A), dtype=torch.float64, device=contracts.device)
+    if B > 0 and c.general:
+        _lib.check(_lib.lib().smc_basket_price_general(
+            _lib.ptr(contracts), _lib.ptr(c.weights), c.w_stride, _lib.ptr(c.tri), c.c_stride, B, A, cfg.timesteps,
+            c.P, cfg.mc_seed, None, ordinal0, c.math, c.norm, _lib.ptr(block), _lib.ptr(tsum), _lib.stream_handle()))
+    elif B > 0:
+        _lib.check(_lib.lib().smc_basket_price(
+            _lib.ptr(contracts), B, A, cfg.timesteps, c.P, cfg.mc_seed, None, ordinal0, c.math, c.norm,
+            _lib.ptr(block), _lib.ptr(tsum), _lib.stream_handle()))
     return BasketPrices(**{name: block[:, col] for col, name in enumerate(PRICE_FIELDS)}, terminal_sum=tsum,
                         block=block)
 
@@ -402,45 +435,14 @@ def basket_price_paths(contracts: torch.Tensor, cfg: BasketConfig, *, barriers: 
     is a level like any other); None switches all three off.  ``weights`` and ``correlation`` as ``basket_price``'s
     (None: 1 / A and the rows' rho).  ``validate=True`` checks the values first (``validate_basket_inputs``, and
     ``validate_basket_barriers``: no NaN, lower < upper) and is the only path that synchronises."""
-    if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
-            not contracts.is_contiguous():
-        raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
-    P = cfg.total_paths if n_paths is None else int(n_paths)
-    if P <= 0:
-        raise ValueError(f"n_paths must be positive, got {n_paths}")
-    B, A = contracts.shape[0], cfg.n_assets
-    if barriers is not None and (not isinstance(barriers, torch.Tensor) or barriers.dtype != torch.float64 or
-                                 not barriers.is_contiguous() or tuple(barriers.shape) != (B, 3)):
-        raise ValueError(f"barriers must be a contiguous float64 tensor of shape ({B}, 3)")
-    w_stride = c_stride = 0
-    packed = True
-    if weights is not None:
-        weights, w_stride = _general_weights(weights, B, A)
-    if correlation is not None:
-        correlation, c_stride, packed = _general_correlation(correlation, B, A)
-    given = (("barriers", barriers), ("weights", weights), ("correlation", correlation))
-    for name, t in given:
-        if t is not None and not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor")
-    _lib.require_device()
-    if not contracts.is_cuda:
-        raise ValueError("contracts must be a device tensor")
-    for name, t in given:
-        if t is not None and t.device != contracts.device:
-            raise ValueError(f"{name} must be on the contracts' device")
-    if validate:
-        validate_basket_inputs(weights, correlation, A)
-        validate_basket_barriers(barriers)
+    c = _batched_call(contracts, cfg, n_paths, weights, correlation, validate, barriers=barriers)
+    B, A = c.B, c.A
     block = torch.empty((B, _lib.BASKET_PATH_COLS), dtype=torch.float64, device=contracts.device)
     tsum = torch.empty((B, A), dtype=torch.float64, device=contracts.device)
     if B > 0:
-        tri = correlation if packed else pack_correlation(correlation)
-        if tri is not None and tri.numel() == 0:  # A = 1: no entry to read
-            tri = None
         _lib.check(_lib.lib().smc_basket_price_paths(
-            _lib.ptr(contracts), _lib.ptr(weights), w_stride, _lib.ptr(tri), c_stride, _lib.ptr(barriers), B, A,
-            cfg.timesteps, P, cfg.mc_seed, None, ordinal0, _lib.MATH_HW if cfg.math == "hw" else 0,
-            _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW, _lib.ptr(block), _lib.ptr(tsum),
+            _lib.ptr(contracts), _lib.ptr(c.weights), c.w_stride, _lib.ptr(c.tri), c.c_stride, _lib.ptr(barriers), B,
+            A, cfg.timesteps, c.P, cfg.mc_seed, None, ordinal0, c.math, c.norm, _lib.ptr(block), _lib.ptr(tsum),
             _lib.stream_handle()))
     return BasketPathPrices(**{name: block[:, col] for col, name in enumerate(BASKET_PATH_FIELDS)}, terminal_sum=tsum,
                             block=block)
@@ -588,54 +590,25 @@ def basket_greeks(contracts: torch.Tensor, cfg: BasketConfig, *, ordinal0: int =
     are then those of the weighted basket (a negative weight flips their sign by itself) and the correlation
     sensitivity is reported per pair.  ``validate=True`` checks the values first (``validate_basket_inputs``) and is
     the only path that synchronises."""
-    if contracts.dim() != 2 or contracts.dtype != torch.float64 or contracts.shape[1] != cfg.dim or \
-            not contracts.is_contiguous():
-        raise ValueError(f"contracts must be a contiguous (B, {cfg.dim}) float64 tensor")
-    P = cfg.total_paths if n_paths is None else int(n_paths)
-    if P <= 0:
-        raise ValueError(f"n_paths must be positive, got {n_paths}")
-    B, A = contracts.shape[0], cfg.n_assets
-    general = weights is not None or correlation is not None
-    w_stride = c_stride = 0
-    packed = True
-    if weights is not None:
-        weights, w_stride = _general_weights(weights, B, A)
-    if correlation is not None:
-        correlation, c_stride, packed = _general_correlation(correlation, B, A)
-    for name, t in (("weights", weights), ("correlation", correlation)):
-        if t is not None and not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor")
-    _lib.require_device()
-    if not contracts.is_cuda:
-        raise ValueError("contracts must be a device tensor")
-    for name, t in (("weights", weights), ("correlation", correlation)):
-        if t is not None and t.device != contracts.device:
-            raise ValueError(f"{name} must be on the contracts' device")
-    if validate:
-        validate_basket_inputs(weights, correlation, A)
-    if general:
+    c = _batched_call(contracts, cfg, n_paths, weights, correlation, validate, replay=replay)
+    B, A = c.B, c.A
+    if c.general:
         block = torch.empty((B, _lib.basket_greeks_general_cols(A)), dtype=torch.float64, device=contracts.device)
         nm = A * (A + 1) // 2
         sums = torch.empty((B, A + nm), dtype=torch.float64, device=contracts.device)
         if B > 0:
-            math = (_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0)
-            tri = correlation if packed else pack_correlation(correlation)
-            if tri is not None and tri.numel() == 0:  # A = 1: no entry to read
-                tri = None
             _lib.check(_lib.lib().smc_basket_greeks_general(
-                _lib.ptr(contracts), _lib.ptr(weights), w_stride, _lib.ptr(tri), c_stride, B, A, cfg.timesteps, P,
-                cfg.mc_seed, None, ordinal0, math, _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW,
-                _lib.ptr(block), _lib.ptr(sums), _lib.stream_handle()))
+                _lib.ptr(contracts), _lib.ptr(c.weights), c.w_stride, _lib.ptr(c.tri), c.c_stride, B, A, cfg.timesteps,
+                c.P, cfg.mc_seed, None, ordinal0, c.math, c.norm, _lib.ptr(block), _lib.ptr(sums),
+                _lib.stream_handle()))
         return BasketGeneralGreeks(**_general_greeks_views(block, A), terminal_sum=sums[:, :A], sum_moments=sums[:, A:],
                                    block=block)
     block = torch.empty((B, _lib.basket_greeks_cols(A)), dtype=torch.float64, device=contracts.device)
     sums = torch.empty((B, 3, A), dtype=torch.float64, device=contracts.device)
     if B > 0:
-        math = (_lib.MATH_HW if cfg.math == "hw" else 0) | (_lib.PRICE_REPLAY if replay else 0)
         _lib.check(_lib.lib().smc_basket_greeks(
-            _lib.ptr(contracts), B, A, cfg.timesteps, P, cfg.mc_seed, None, ordinal0, math,
-            _lib.NORM_NORMALIZE if cfg.normalize else _lib.NORM_RAW, _lib.ptr(block), _lib.ptr(sums),
-            _lib.stream_handle()))
+            _lib.ptr(contracts), B, A, cfg.timesteps, c.P, cfg.mc_seed, None, ordinal0, c.math, c.norm,
+            _lib.ptr(block), _lib.ptr(sums), _lib.stream_handle()))
     return BasketGreeks(**_greeks_views(block, A), terminal_sum=sums[:, 0], sum_xl=sums[:, 1], sum_xc=sums[:, 2],
                         block=block)
 

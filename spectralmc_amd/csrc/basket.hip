@@ -2267,6 +2267,57 @@ size_t basket_cf_lds_bytes(int N) {
 // (as the single-asset paths_kernel + cf_kernel pair; kBasketSplit = false keeps the fused kernel)
 constexpr bool kBasketSplit = true;
 
+// ---- The host layer: one dispatch, one launch path, one mode rule and one argument screen for every kernel ----
+
+// A run-time value as a compile-time constant: f is a generic callable and is handed a std::integral_constant.
+// n_assets -> A in 1..8; any other count is "<entry>: n_assets must be in 1..8".
+template <typename F>
+auto with_assets(int n_assets, const char* entry, F&& f) -> decltype(f(std::integral_constant<int, 1>{})) {
+  switch (n_assets) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: set_error("%s: n_assets must be in 1..8", entry); return SMC_ERR_INVALID_ARGUMENT;
+  }
+}
+
+template <typename F>
+auto with_flag(bool on, F&& f) -> decltype(f(std::true_type{})) {
+  return on ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// (A, HW) of a call: f(A, HW), HW from math & SMC_MATH_HW
+template <typename F>
+auto with_variant(int n_assets, bool hw, const char* entry, F&& f) {
+  return with_assets(n_assets, entry, [&](auto A) { return with_flag(hw, [&](auto HW) { return f(A, HW); }); });
+}
+
+template <typename F>
+auto with_price_mode(int mode, F&& f) -> decltype(f(std::integral_constant<int, kBPriceRaw>{})) {
+  return mode == kBPriceRaw   ? f(std::integral_constant<int, kBPriceRaw>{})
+         : mode == kBPriceLds ? f(std::integral_constant<int, kBPriceLds>{})
+                              : f(std::integral_constant<int, kBPriceReplay>{});
+}
+
+// One workgroup of kBThreads per contract with `lds` bytes of dynamic LDS (the limit raised where it is above 64 KiB).
+template <typename K, typename... Args>
+int32_t launch_per_contract(K kernel, const char* name, int64_t B, size_t lds, hipStream_t stream, Args... args) {
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: cannot raise the dynamic LDS limit", name);
+    return SMC_ERR_HIP;
+  }
+  launch(kernel, dim3(static_cast<unsigned>(B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, args...);
+  return check_launch(name);
+}
+
 template <int A, bool HW>
 const void* basket_kernel_ptr() {
   return reinterpret_cast<const void*>(basket_kernel<A, HW, kBasketSplit ? 1 : 0>);
@@ -2288,34 +2339,22 @@ int64_t basket_slots_k(int N) {
   return static_cast<int64_t>(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
 }
 
-template <int A, bool HW, int MODE>
-int32_t launch_basket_mode(const BasketArgs& a, hipStream_t stream) {
-  const size_t lds = basket_lds_bytes(A, a.N);
-  auto kernel = basket_kernel<A, HW, MODE>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SMC_ERR_HIP, "basket_kernel: cannot raise the dynamic LDS limit");
-  }
-  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), lds, stream, a);
-  return check_launch("basket_kernel");
+int64_t basket_slots(int n_assets, bool hw, int N) {
+  if (n_assets < 1 || n_assets > kMaxAssets) return -1;
+  return with_variant(n_assets, hw, "basket", [&](auto A, auto HW) { return basket_slots_k<A(), HW()>(N); });
 }
 
 template <int A, bool HW>
 int32_t launch_basket_k(const BasketArgs& a, hipStream_t stream) {
-  if (!kBasketSplit || !a.terminal_sum) return launch_basket_mode<A, HW, 0>(a, stream);
-  if (int32_t st = launch_basket_mode<A, HW, 1>(a, stream)) return st;
-  const size_t lds = basket_cf_lds_bytes(a.N);
-  auto cf = basket_cf_kernel<A>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(cf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SMC_ERR_HIP, "basket_cf_kernel: cannot raise the dynamic LDS limit");
-  }
-  launch(cf, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), lds, stream, a);
-  return check_launch("basket_cf_kernel");
+  const size_t lds = basket_lds_bytes(A, a.N);
+  if (!kBasketSplit || !a.terminal_sum)
+    return launch_per_contract(basket_kernel<A, HW, 0>, "basket_kernel", a.B, lds, stream, a);
+  if (int32_t st = launch_per_contract(basket_kernel<A, HW, 1>, "basket_kernel", a.B, lds, stream, a)) return st;
+  return launch_per_contract(basket_cf_kernel<A>, "basket_cf_kernel", a.B, basket_cf_lds_bytes(a.N), stream, a);
+}
+
+int32_t launch_basket(int n_assets, bool hw, const BasketArgs& a, hipStream_t stream) {
+  return with_variant(n_assets, hw, "basket", [&](auto A, auto HW) { return launch_basket_k<A(), HW()>(a, stream); });
 }
 
 // Workgroups per contract of basket_resident_kernel for this shape, or 0 when it does not take it
@@ -2363,246 +2402,143 @@ int32_t launch_basket_resident_k(const BasketArgs& a, int W, int64_t groups, int
   return check_launch("basket_mean_fft_kernel");
 }
 
-template <bool HW>
-int32_t launch_basket_resident(int A, const BasketArgs& a, int W, int64_t groups, int64_t chunk, uint8_t* sync,
-                               hipStream_t stream) {
-  switch (A) {
-    case 1: return launch_basket_resident_k<1, HW>(a, W, groups, chunk, sync, stream);
-    case 2: return launch_basket_resident_k<2, HW>(a, W, groups, chunk, sync, stream);
-    case 3: return launch_basket_resident_k<3, HW>(a, W, groups, chunk, sync, stream);
-    case 4: return launch_basket_resident_k<4, HW>(a, W, groups, chunk, sync, stream);
-    case 5: return launch_basket_resident_k<5, HW>(a, W, groups, chunk, sync, stream);
-    case 6: return launch_basket_resident_k<6, HW>(a, W, groups, chunk, sync, stream);
-    case 7: return launch_basket_resident_k<7, HW>(a, W, groups, chunk, sync, stream);
-    case 8: return launch_basket_resident_k<8, HW>(a, W, groups, chunk, sync, stream);
-    default: return fail(SMC_ERR_INVALID_ARGUMENT, "basket: n_assets must be in 1..8");
-  }
+int32_t launch_basket_resident(int n_assets, bool hw, const BasketArgs& a, int W, int64_t groups, int64_t chunk,
+                               uint8_t* sync, hipStream_t stream) {
+  return with_variant(n_assets, hw, "basket", [&](auto A, auto HW) {
+    return launch_basket_resident_k<A(), HW()>(a, W, groups, chunk, sync, stream);
+  });
 }
 
-template <bool HW>
-int64_t basket_slots(int A, int N) {
-  switch (A) {
-    case 1: return basket_slots_k<1, HW>(N);
-    case 2: return basket_slots_k<2, HW>(N);
-    case 3: return basket_slots_k<3, HW>(N);
-    case 4: return basket_slots_k<4, HW>(N);
-    case 5: return basket_slots_k<5, HW>(N);
-    case 6: return basket_slots_k<6, HW>(N);
-    case 7: return basket_slots_k<7, HW>(N);
-    case 8: return basket_slots_k<8, HW>(N);
-    default: return -1;
-  }
+// What the five batched entry points share: the entry's name (for its messages) and the arguments all of them take.
+struct BasketCall {
+  const char* entry;
+  const double* contracts;
+  int64_t B;
+  int32_t A, T;
+  int64_t P;
+  uint64_t seed;
+  const int64_t* ordinal_dev;
+  int64_t ordinal0;
+  int32_t math, normalization;
+};
+
+int32_t fail_in(const char* entry, int32_t code, const char* what) {
+  set_error("%s: %s", entry, what);
+  return code;
 }
 
-template <bool HW>
-int32_t launch_basket(int A, const BasketArgs& a, hipStream_t stream) {
-  switch (A) {
-    case 1: return launch_basket_k<1, HW>(a, stream);
-    case 2: return launch_basket_k<2, HW>(a, stream);
-    case 3: return launch_basket_k<3, HW>(a, stream);
-    case 4: return launch_basket_k<4, HW>(a, stream);
-    case 5: return launch_basket_k<5, HW>(a, stream);
-    case 6: return launch_basket_k<6, HW>(a, stream);
-    case 7: return launch_basket_k<7, HW>(a, stream);
-    case 8: return launch_basket_k<8, HW>(a, stream);
-    default: return fail(SMC_ERR_INVALID_ARGUMENT, "basket: n_assets must be in 1..8");
+// The shared checks, in the order every entry makes them; out_name names the entry's output block.
+int32_t check_basket_call(const BasketCall& c, const char* out_name, const void* out) {
+  if (!c.contracts) return fail_in(c.entry, SMC_ERR_INVALID_ARGUMENT, "contracts_dev is NULL");
+  if (!out) {
+    set_error("%s: %s is NULL", c.entry, out_name);
+    return SMC_ERR_INVALID_ARGUMENT;
   }
+  if (c.A < 1 || c.A > kMaxAssets) return fail_in(c.entry, SMC_ERR_INVALID_ARGUMENT, "n_assets must be in 1..8");
+  if (c.math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
+    return fail_in(c.entry, SMC_ERR_INVALID_ARGUMENT, "bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
+  if (c.normalization != SMC_NORM_RAW && c.normalization != SMC_NORM_NORMALIZE)
+    return fail_in(c.entry, SMC_ERR_INVALID_ARGUMENT, "bad normalization");
+  if (c.B < 0 || c.B > 0x7fffffffLL || c.T <= 0 || c.P <= 0)
+    return fail_in(c.entry, SMC_ERR_INVALID_SHAPE, "need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
+  if (c.P >= (int64_t{1} << 40)) return fail_in(c.entry, SMC_ERR_INVALID_SHAPE, "n_paths too large (>= 2^40)");
+  return SMC_OK;
 }
 
-// basket_price_kernel's mode and dynamic LDS for a shape (host only, no HIP call); -1: not a call it takes.
-// math: 0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY.
-int basket_price_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
-  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
-  *lds = kBPriceScratch;
+int32_t check_basket_strides(const BasketCall& c, const double* weights, int64_t weights_stride, const double* corr,
+                             int64_t corr_stride) {
+  if (weights && weights_stride != 0 && weights_stride < c.A)
+    return fail_in(c.entry, SMC_ERR_INVALID_ARGUMENT, "weights_stride must be 0 or >= n_assets");
+  if (corr && corr_stride != 0 && corr_stride < c.A * (c.A - 1) / 2)
+    return fail_in(c.entry, SMC_ERR_INVALID_ARGUMENT, "corr_stride must be 0 or >= n_assets (n_assets - 1) / 2");
+  return SMC_OK;
+}
+
+BasketArgs basket_args(const BasketCall& c, double* terminal_sum) {
+  BasketArgs a{};
+  a.contracts = c.contracts;
+  a.B = c.B;
+  a.T = c.T;
+  a.P = c.P;
+  a.seed = c.seed;
+  a.ordinal_dev = c.ordinal_dev;
+  a.ordinal0 = c.ordinal0;
+  a.normalize = c.normalization != SMC_NORM_RAW;
+  a.terminal_sum = terminal_sum;
+  return a;
+}
+
+BasketGeneralArgs basket_general_args(const BasketCall& c, const double* weights, int64_t weights_stride,
+                                      const double* corr, int64_t corr_stride) {
+  // A = 1 has no correlation entry: nothing to read, whatever the caller passed
+  return BasketGeneralArgs{weights, weights_stride, c.A > 1 ? corr : nullptr, corr_stride};
+}
+
+// The screen of every plan below (host only, no HIP call): a shape and flags the batched kernels take.
+bool basket_plan_ok(int A, int64_t P, int32_t math, int32_t normalization) {
+  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return false;
+  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return false;
+  return normalization == SMC_NORM_RAW || normalization == SMC_NORM_NORMALIZE;
+}
+
+// A kernel under the raw / lds / replay rule: its name, the scratch bytes at the head of its dynamic LDS and what
+// its smc_*_kernel entry reports per mode (BasketPriceMode's order).
+struct ParkKernel {
+  const char* name;
+  size_t scratch;
+  const char* mode_name[3];
+};
+constexpr ParkKernel kParkPrice{"basket_price_kernel", kBPriceScratch,
+                                {"basket_price_kernel(raw)", "basket_price_kernel(lds)", "basket_price_kernel(replay)"}};
+constexpr ParkKernel kParkGeneral{
+    "basket_general_kernel", kBGeneralScratch,
+    {"basket_general_kernel(raw)", "basket_general_kernel(lds)", "basket_general_kernel(replay)"}};
+constexpr ParkKernel kParkGreeks{
+    "basket_greeks_kernel", kBGreekScratch,
+    {"basket_greeks_kernel(raw)", "basket_greeks_kernel(lds)", "basket_greeks_kernel(replay)"}};
+constexpr ParkKernel kParkGreeksGeneral{
+    "basket_greeks_general_kernel", kBGGScratch,
+    {"basket_greeks_general_kernel(raw)", "basket_greeks_general_kernel(lds)", "basket_greeks_general_kernel(replay)"}};
+
+// A ParkKernel's mode and dynamic LDS for a shape (host only, no HIP call); -1: not a call it takes.
+// math: 0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY.  NORMALIZE parks the terminal values in LDS while the
+// scratch and [A][P rounded up to 4] floats fit kBPriceParkBytes, and replays the streams beyond.
+int basket_park_mode(const ParkKernel& k, int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
+  if (!basket_plan_ok(A, P, math, normalization)) return -1;
+  *lds = k.scratch;
   if (normalization == SMC_NORM_RAW) return kBPriceRaw;
   if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
-  const size_t park = kBPriceScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
+  const size_t park = k.scratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
   if (park > kBPriceParkBytes) return kBPriceReplay;
   *lds = park;
   return kBPriceLds;
 }
 
-template <int A, bool HW>
-int32_t launch_basket_price_k(const BasketArgs& a, int mode, size_t lds, double* prices, hipStream_t stream) {
-  auto kernel = mode == kBPriceRaw   ? basket_price_kernel<A, HW, kBPriceRaw>
-                : mode == kBPriceLds ? basket_price_kernel<A, HW, kBPriceLds>
-                                     : basket_price_kernel<A, HW, kBPriceReplay>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SMC_ERR_HIP, "basket_price_kernel: cannot raise the dynamic LDS limit");
-  }
-  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, prices);
-  return check_launch("basket_price_kernel");
+const char* park_kernel_name(const ParkKernel& k, int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                             int32_t normalization) {
+  size_t lds = 0;
+  if (timesteps <= 0) return "unsupported";
+  const int mode = basket_park_mode(k, n_assets, n_paths, math, normalization, &lds);
+  return mode < 0 ? "unsupported" : k.mode_name[mode];
 }
 
-template <bool HW>
-int32_t launch_basket_price(int A, const BasketArgs& a, int mode, size_t lds, double* prices, hipStream_t stream) {
-  switch (A) {
-    case 1: return launch_basket_price_k<1, HW>(a, mode, lds, prices, stream);
-    case 2: return launch_basket_price_k<2, HW>(a, mode, lds, prices, stream);
-    case 3: return launch_basket_price_k<3, HW>(a, mode, lds, prices, stream);
-    case 4: return launch_basket_price_k<4, HW>(a, mode, lds, prices, stream);
-    case 5: return launch_basket_price_k<5, HW>(a, mode, lds, prices, stream);
-    case 6: return launch_basket_price_k<6, HW>(a, mode, lds, prices, stream);
-    case 7: return launch_basket_price_k<7, HW>(a, mode, lds, prices, stream);
-    case 8: return launch_basket_price_k<8, HW>(a, mode, lds, prices, stream);
-    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: n_assets must be in 1..8");
-  }
-}
-
-// basket_general_kernel's mode and dynamic LDS for a shape (host only, no HIP call): basket_price_mode's rule with
-// this kernel's scratch in the park bound; -1: not a call it takes.
-int basket_general_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
-  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
-  *lds = kBGeneralScratch;
-  if (normalization == SMC_NORM_RAW) return kBPriceRaw;
-  if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
-  const size_t park = kBGeneralScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
-  if (park > kBPriceParkBytes) return kBPriceReplay;
-  *lds = park;
-  return kBPriceLds;
-}
-
-template <int A, bool HW>
-int32_t launch_basket_general_k(const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds, double* prices,
-                                hipStream_t stream) {
-  auto kernel = mode == kBPriceRaw   ? basket_general_kernel<A, HW, kBPriceRaw>
-                : mode == kBPriceLds ? basket_general_kernel<A, HW, kBPriceLds>
-                                     : basket_general_kernel<A, HW, kBPriceReplay>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SMC_ERR_HIP, "basket_general_kernel: cannot raise the dynamic LDS limit");
-  }
-  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, g, prices);
-  return check_launch("basket_general_kernel");
-}
-
-template <bool HW>
-int32_t launch_basket_general(int A, const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds,
-                              double* prices, hipStream_t stream) {
-  switch (A) {
-    case 1: return launch_basket_general_k<1, HW>(a, g, mode, lds, prices, stream);
-    case 2: return launch_basket_general_k<2, HW>(a, g, mode, lds, prices, stream);
-    case 3: return launch_basket_general_k<3, HW>(a, g, mode, lds, prices, stream);
-    case 4: return launch_basket_general_k<4, HW>(a, g, mode, lds, prices, stream);
-    case 5: return launch_basket_general_k<5, HW>(a, g, mode, lds, prices, stream);
-    case 6: return launch_basket_general_k<6, HW>(a, g, mode, lds, prices, stream);
-    case 7: return launch_basket_general_k<7, HW>(a, g, mode, lds, prices, stream);
-    case 8: return launch_basket_general_k<8, HW>(a, g, mode, lds, prices, stream);
-    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: n_assets must be in 1..8");
-  }
-}
-
-// basket_greeks_kernel's mode and dynamic LDS for a shape (host only, no HIP call): basket_price_mode's rule with
-// this kernel's scratch in the park bound; -1: not a call it takes.
-int basket_greeks_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
-  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
-  *lds = kBGreekScratch;
-  if (normalization == SMC_NORM_RAW) return kBPriceRaw;
-  if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
-  const size_t park = kBGreekScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
-  if (park > kBPriceParkBytes) return kBPriceReplay;
-  *lds = park;
-  return kBPriceLds;
-}
-
-template <int A, bool HW>
-int32_t launch_basket_greeks_k(const BasketArgs& a, int mode, size_t lds, double* greeks, double* sums,
-                               hipStream_t stream) {
-  auto kernel = mode == kBPriceRaw   ? basket_greeks_kernel<A, HW, kBPriceRaw>
-                : mode == kBPriceLds ? basket_greeks_kernel<A, HW, kBPriceLds>
-                                     : basket_greeks_kernel<A, HW, kBPriceReplay>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SMC_ERR_HIP, "basket_greeks_kernel: cannot raise the dynamic LDS limit");
-  }
-  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, greeks, sums);
-  return check_launch("basket_greeks_kernel");
-}
-
-template <bool HW>
-int32_t launch_basket_greeks(int A, const BasketArgs& a, int mode, size_t lds, double* greeks, double* sums,
-                             hipStream_t stream) {
-  switch (A) {
-    case 1: return launch_basket_greeks_k<1, HW>(a, mode, lds, greeks, sums, stream);
-    case 2: return launch_basket_greeks_k<2, HW>(a, mode, lds, greeks, sums, stream);
-    case 3: return launch_basket_greeks_k<3, HW>(a, mode, lds, greeks, sums, stream);
-    case 4: return launch_basket_greeks_k<4, HW>(a, mode, lds, greeks, sums, stream);
-    case 5: return launch_basket_greeks_k<5, HW>(a, mode, lds, greeks, sums, stream);
-    case 6: return launch_basket_greeks_k<6, HW>(a, mode, lds, greeks, sums, stream);
-    case 7: return launch_basket_greeks_k<7, HW>(a, mode, lds, greeks, sums, stream);
-    case 8: return launch_basket_greeks_k<8, HW>(a, mode, lds, greeks, sums, stream);
-    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: n_assets must be in 1..8");
-  }
-}
-
-// basket_greeks_general_kernel's mode and dynamic LDS for a shape (host only, no HIP call): basket_price_mode's rule
-// with this kernel's scratch in the park bound; -1: not a call it takes.
-int basket_greeks_general_mode(int A, int64_t P, int32_t math, int32_t normalization, size_t* lds) {
-  if (A < 1 || A > kMaxAssets || P <= 0 || P >= (int64_t{1} << 40)) return -1;
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
-  *lds = kBGGScratch;
-  if (normalization == SMC_NORM_RAW) return kBPriceRaw;
-  if (math & SMC_PRICE_REPLAY) return kBPriceReplay;
-  const size_t park = kBGGScratch + static_cast<size_t>(A) * ((static_cast<size_t>(P) + 3) & ~size_t{3}) * sizeof(float);
-  if (park > kBPriceParkBytes) return kBPriceReplay;
-  *lds = park;
-  return kBPriceLds;
-}
-
-template <int A, bool HW>
-int32_t launch_basket_greeks_general_k(const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds,
-                                       double* greeks, double* sums, hipStream_t stream) {
-  auto kernel = mode == kBPriceRaw   ? basket_greeks_general_kernel<A, HW, kBPriceRaw>
-                : mode == kBPriceLds ? basket_greeks_general_kernel<A, HW, kBPriceLds>
-                                     : basket_greeks_general_kernel<A, HW, kBPriceReplay>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SMC_ERR_HIP, "basket_greeks_general_kernel: cannot raise the dynamic LDS limit");
-  }
-  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, g, greeks,
-         sums);
-  return check_launch("basket_greeks_general_kernel");
-}
-
-template <bool HW>
-int32_t launch_basket_greeks_general(int A, const BasketArgs& a, const BasketGeneralArgs& g, int mode, size_t lds,
-                                     double* greeks, double* sums, hipStream_t stream) {
-  switch (A) {
-    case 1: return launch_basket_greeks_general_k<1, HW>(a, g, mode, lds, greeks, sums, stream);
-    case 2: return launch_basket_greeks_general_k<2, HW>(a, g, mode, lds, greeks, sums, stream);
-    case 3: return launch_basket_greeks_general_k<3, HW>(a, g, mode, lds, greeks, sums, stream);
-    case 4: return launch_basket_greeks_general_k<4, HW>(a, g, mode, lds, greeks, sums, stream);
-    case 5: return launch_basket_greeks_general_k<5, HW>(a, g, mode, lds, greeks, sums, stream);
-    case 6: return launch_basket_greeks_general_k<6, HW>(a, g, mode, lds, greeks, sums, stream);
-    case 7: return launch_basket_greeks_general_k<7, HW>(a, g, mode, lds, greeks, sums, stream);
-    case 8: return launch_basket_greeks_general_k<8, HW>(a, g, mode, lds, greeks, sums, stream);
-    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: n_assets must be in 1..8");
-  }
+// The launch of a checked call of a ParkKernel: pick(A, HW, MODE) names the kernel's instance, args follow `a`.
+template <typename Pick, typename... Args>
+int32_t launch_parked(const BasketCall& c, const ParkKernel& k, hipStream_t stream, Pick pick, Args... args) {
+  size_t lds = 0;
+  const int mode = basket_park_mode(k, c.A, c.P, c.math, c.normalization, &lds);
+  return with_variant(c.A, c.math & SMC_MATH_HW, c.entry, [&](auto A, auto HW) {
+    return with_price_mode(mode, [&](auto MODE) {
+      return launch_per_contract(pick(A, HW, MODE), k.name, c.B, lds, stream, args...);
+    });
+  });
 }
 
 // basket_path_kernel's plan for a shape (host only, no HIP call): 0 one RAW simulation per column group, 1 the
 // NORMALIZE replay, -1 not a call it takes, -2 more scales (A T) than LDS holds beside one date of accumulators.
 // *dates is the number of whole time rows per sweep (NORMALIZE), *lds the dynamic LDS.
 int basket_path_plan(int A, int32_t T, int64_t P, int32_t math, int32_t normalization, size_t* lds, int* dates) {
-  if (A < 1 || A > kMaxAssets || T <= 0 || P <= 0 || P >= (int64_t{1} << 40)) return -1;
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY)) return -1;
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE) return -1;
+  if (T <= 0 || !basket_plan_ok(A, P, math, normalization)) return -1;
   *dates = 0;
   *lds = kBPathScratch + static_cast<size_t>(A) * kBPathAccRow;
   if (normalization == SMC_NORM_RAW) return 0;
@@ -2612,37 +2548,6 @@ int basket_path_plan(int A, int32_t T, int64_t P, int32_t math, int32_t normaliz
   *dates = static_cast<int>(static_cast<size_t>(T) < fit ? static_cast<size_t>(T) : fit);
   *lds = head + static_cast<size_t>(*dates) * A * kBPathAccRow;
   return 1;
-}
-
-template <int A, bool HW>
-int32_t launch_basket_path_k(const BasketArgs& a, const BasketGeneralArgs& g, const double* barriers, size_t lds,
-                             int dates, double* prices, hipStream_t stream) {
-  auto kernel = a.normalize ? basket_path_kernel<A, HW, true> : basket_path_kernel<A, HW, false>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SMC_ERR_HIP, "basket_path_kernel: cannot raise the dynamic LDS limit");
-  }
-  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kBThreads), static_cast<uint32_t>(lds), stream, a, g, barriers,
-         prices, dates);
-  return check_launch("basket_path_kernel");
-}
-
-template <bool HW>
-int32_t launch_basket_path(int A, const BasketArgs& a, const BasketGeneralArgs& g, const double* barriers, size_t lds,
-                           int dates, double* prices, hipStream_t stream) {
-  switch (A) {
-    case 1: return launch_basket_path_k<1, HW>(a, g, barriers, lds, dates, prices, stream);
-    case 2: return launch_basket_path_k<2, HW>(a, g, barriers, lds, dates, prices, stream);
-    case 3: return launch_basket_path_k<3, HW>(a, g, barriers, lds, dates, prices, stream);
-    case 4: return launch_basket_path_k<4, HW>(a, g, barriers, lds, dates, prices, stream);
-    case 5: return launch_basket_path_k<5, HW>(a, g, barriers, lds, dates, prices, stream);
-    case 6: return launch_basket_path_k<6, HW>(a, g, barriers, lds, dates, prices, stream);
-    case 7: return launch_basket_path_k<7, HW>(a, g, barriers, lds, dates, prices, stream);
-    case 8: return launch_basket_path_k<8, HW>(a, g, barriers, lds, dates, prices, stream);
-    default: return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: n_assets must be in 1..8");
-  }
 }
 
 }  // namespace
@@ -2704,12 +2609,10 @@ int32_t smc_basket_train_targets(const double* contracts_dev, int64_t n_contract
                  terminal_sum_dev ? terminal_sum_dev + off * n_assets : nullptr,
                  static_cast<float2*>(targets_dev) + off * N};
     uint8_t* sync = static_cast<uint8_t*>(sync_dev);
+    const bool hw = math == SMC_MATH_HW;
     const int32_t st =
-        W > 0 ? (math == SMC_MATH_HW
-                     ? launch_basket_resident<true>(n_assets, a, W, groups, chunk_contracts, sync, as_stream(stream))
-                     : launch_basket_resident<false>(n_assets, a, W, groups, chunk_contracts, sync, as_stream(stream)))
-              : (math == SMC_MATH_HW ? launch_basket<true>(n_assets, a, as_stream(stream))
-                                     : launch_basket<false>(n_assets, a, as_stream(stream)));
+        W > 0 ? launch_basket_resident(n_assets, hw, a, W, groups, chunk_contracts, sync, as_stream(stream))
+              : launch_basket(n_assets, hw, a, as_stream(stream));
     if (st) return st;
   }
   return SMC_OK;
@@ -2736,50 +2639,23 @@ const char* smc_basket_train_targets_kernel(int32_t n_assets, int32_t timesteps,
 
 int64_t smc_basket_resident_slots(int32_t n_assets, int32_t network_size, int32_t math) {
   if (n_assets < 1 || n_assets > kMaxAssets || network_size <= 0 || network_size > 4096) return -1;
-  return math == SMC_MATH_HW ? basket_slots<true>(n_assets, network_size) : basket_slots<false>(n_assets, network_size);
+  return basket_slots(n_assets, math == SMC_MATH_HW, network_size);
 }
 
 int32_t smc_basket_price(const double* contracts_dev, int64_t n_contracts, int32_t n_assets, int32_t timesteps,
                          int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
                          int32_t normalization, double* prices_dev, double* terminal_sum_dev, void* stream) {
-  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: contracts_dev is NULL");
-  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: prices_dev is NULL");
-  if (n_assets < 1 || n_assets > kMaxAssets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: n_assets must be in 1..8");
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price: bad normalization");
-  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
-    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
-  if (n_paths >= (int64_t{1} << 40)) return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price: n_paths too large (>= 2^40)");
+  const BasketCall c{"smc_basket_price", contracts_dev, n_contracts, n_assets, timesteps, n_paths,
+                     mc_seed, ordinal_dev, ordinal0, math, normalization};
+  if (int32_t st = check_basket_call(c, "prices_dev", prices_dev)) return st;
   if (n_contracts == 0) return SMC_OK;
-  size_t lds = 0;
-  const int mode = basket_price_mode(n_assets, n_paths, math, normalization, &lds);
-  BasketArgs a{};
-  a.contracts = contracts_dev;
-  a.B = n_contracts;
-  a.T = timesteps;
-  a.P = n_paths;
-  a.seed = mc_seed;
-  a.ordinal_dev = ordinal_dev;
-  a.ordinal0 = ordinal0;
-  a.normalize = normalization != SMC_NORM_RAW;
-  a.terminal_sum = terminal_sum_dev;
-  return (math & SMC_MATH_HW) ? launch_basket_price<true>(n_assets, a, mode, lds, prices_dev, as_stream(stream))
-                              : launch_basket_price<false>(n_assets, a, mode, lds, prices_dev, as_stream(stream));
+  const auto pick = [](auto A, auto HW, auto MODE) { return basket_price_kernel<A(), HW(), MODE()>; };
+  return launch_parked(c, kParkPrice, as_stream(stream), pick, basket_args(c, terminal_sum_dev), prices_dev);
 }
 
 const char* smc_basket_price_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
                                     int32_t normalization) {
-  size_t lds = 0;
-  if (timesteps <= 0) return "unsupported";
-  switch (basket_price_mode(n_assets, n_paths, math, normalization, &lds)) {
-    case kBPriceRaw: return "basket_price_kernel(raw)";
-    case kBPriceLds: return "basket_price_kernel(lds)";
-    case kBPriceReplay: return "basket_price_kernel(replay)";
-    default: return "unsupported";
-  }
+  return park_kernel_name(kParkPrice, n_assets, timesteps, n_paths, math, normalization);
 }
 
 int32_t smc_basket_price_general(const double* contracts_dev, const double* weights_dev, int64_t weights_stride,
@@ -2787,98 +2663,35 @@ int32_t smc_basket_price_general(const double* contracts_dev, const double* weig
                                  int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
                                  int64_t ordinal0, int32_t math, int32_t normalization, double* prices_dev,
                                  double* terminal_sum_dev, void* stream) {
-  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: contracts_dev is NULL");
-  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: prices_dev is NULL");
-  if (n_assets < 1 || n_assets > kMaxAssets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: n_assets must be in 1..8");
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
-    return fail(SMC_ERR_INVALID_ARGUMENT,
-                "smc_basket_price_general: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: bad normalization");
-  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
-    return fail(SMC_ERR_INVALID_SHAPE,
-                "smc_basket_price_general: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
-  if (n_paths >= (int64_t{1} << 40))
-    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price_general: n_paths too large (>= 2^40)");
-  if (weights_dev && weights_stride != 0 && weights_stride < n_assets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_general: weights_stride must be 0 or >= n_assets");
-  if (corr_dev && corr_stride != 0 && corr_stride < n_assets * (n_assets - 1) / 2)
-    return fail(SMC_ERR_INVALID_ARGUMENT,
-                "smc_basket_price_general: corr_stride must be 0 or >= n_assets (n_assets - 1) / 2");
+  const BasketCall c{"smc_basket_price_general", contracts_dev, n_contracts, n_assets, timesteps, n_paths,
+                     mc_seed, ordinal_dev, ordinal0, math, normalization};
+  if (int32_t st = check_basket_call(c, "prices_dev", prices_dev)) return st;
+  if (int32_t st = check_basket_strides(c, weights_dev, weights_stride, corr_dev, corr_stride)) return st;
   if (n_contracts == 0) return SMC_OK;
-  size_t lds = 0;
-  const int mode = basket_general_mode(n_assets, n_paths, math, normalization, &lds);
-  BasketArgs a{};
-  a.contracts = contracts_dev;
-  a.B = n_contracts;
-  a.T = timesteps;
-  a.P = n_paths;
-  a.seed = mc_seed;
-  a.ordinal_dev = ordinal_dev;
-  a.ordinal0 = ordinal0;
-  a.normalize = normalization != SMC_NORM_RAW;
-  a.terminal_sum = terminal_sum_dev;
-  // A = 1 has no correlation entry: nothing to read, whatever the caller passed
-  const BasketGeneralArgs g{weights_dev, weights_stride, n_assets > 1 ? corr_dev : nullptr, corr_stride};
-  return (math & SMC_MATH_HW)
-             ? launch_basket_general<true>(n_assets, a, g, mode, lds, prices_dev, as_stream(stream))
-             : launch_basket_general<false>(n_assets, a, g, mode, lds, prices_dev, as_stream(stream));
+  const auto pick = [](auto A, auto HW, auto MODE) { return basket_general_kernel<A(), HW(), MODE()>; };
+  return launch_parked(c, kParkGeneral, as_stream(stream), pick, basket_args(c, terminal_sum_dev),
+                       basket_general_args(c, weights_dev, weights_stride, corr_dev, corr_stride), prices_dev);
 }
 
 const char* smc_basket_price_general_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
                                             int32_t normalization) {
-  size_t lds = 0;
-  if (timesteps <= 0) return "unsupported";
-  switch (basket_general_mode(n_assets, n_paths, math, normalization, &lds)) {
-    case kBPriceRaw: return "basket_general_kernel(raw)";
-    case kBPriceLds: return "basket_general_kernel(lds)";
-    case kBPriceReplay: return "basket_general_kernel(replay)";
-    default: return "unsupported";
-  }
+  return park_kernel_name(kParkGeneral, n_assets, timesteps, n_paths, math, normalization);
 }
 
 int32_t smc_basket_greeks(const double* contracts_dev, int64_t n_contracts, int32_t n_assets, int32_t timesteps,
                           int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
                           int32_t normalization, double* greeks_dev, double* sums_dev, void* stream) {
-  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: contracts_dev is NULL");
-  if (!greeks_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: greeks_dev is NULL");
-  if (n_assets < 1 || n_assets > kMaxAssets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: n_assets must be in 1..8");
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks: bad normalization");
-  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
-    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_greeks: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
-  if (n_paths >= (int64_t{1} << 40)) return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_greeks: n_paths too large (>= 2^40)");
+  const BasketCall c{"smc_basket_greeks", contracts_dev, n_contracts, n_assets, timesteps, n_paths,
+                     mc_seed, ordinal_dev, ordinal0, math, normalization};
+  if (int32_t st = check_basket_call(c, "greeks_dev", greeks_dev)) return st;
   if (n_contracts == 0) return SMC_OK;
-  size_t lds = 0;
-  const int mode = basket_greeks_mode(n_assets, n_paths, math, normalization, &lds);
-  BasketArgs a{};
-  a.contracts = contracts_dev;
-  a.B = n_contracts;
-  a.T = timesteps;
-  a.P = n_paths;
-  a.seed = mc_seed;
-  a.ordinal_dev = ordinal_dev;
-  a.ordinal0 = ordinal0;
-  a.normalize = normalization != SMC_NORM_RAW;
-  return (math & SMC_MATH_HW)
-             ? launch_basket_greeks<true>(n_assets, a, mode, lds, greeks_dev, sums_dev, as_stream(stream))
-             : launch_basket_greeks<false>(n_assets, a, mode, lds, greeks_dev, sums_dev, as_stream(stream));
+  const auto pick = [](auto A, auto HW, auto MODE) { return basket_greeks_kernel<A(), HW(), MODE()>; };
+  return launch_parked(c, kParkGreeks, as_stream(stream), pick, basket_args(c, nullptr), greeks_dev, sums_dev);
 }
 
 const char* smc_basket_greeks_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
                                      int32_t normalization) {
-  size_t lds = 0;
-  if (timesteps <= 0) return "unsupported";
-  switch (basket_greeks_mode(n_assets, n_paths, math, normalization, &lds)) {
-    case kBPriceRaw: return "basket_greeks_kernel(raw)";
-    case kBPriceLds: return "basket_greeks_kernel(lds)";
-    case kBPriceReplay: return "basket_greeks_kernel(replay)";
-    default: return "unsupported";
-  }
+  return park_kernel_name(kParkGreeks, n_assets, timesteps, n_paths, math, normalization);
 }
 
 int32_t smc_basket_greeks_cols(int32_t n_assets) {
@@ -2890,54 +2703,19 @@ int32_t smc_basket_greeks_general(const double* contracts_dev, const double* wei
                                   int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
                                   int64_t ordinal0, int32_t math, int32_t normalization, double* greeks_dev,
                                   double* sums_dev, void* stream) {
-  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: contracts_dev is NULL");
-  if (!greeks_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: greeks_dev is NULL");
-  if (n_assets < 1 || n_assets > kMaxAssets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: n_assets must be in 1..8");
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
-    return fail(SMC_ERR_INVALID_ARGUMENT,
-                "smc_basket_greeks_general: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: bad normalization");
-  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
-    return fail(SMC_ERR_INVALID_SHAPE,
-                "smc_basket_greeks_general: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
-  if (n_paths >= (int64_t{1} << 40))
-    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_greeks_general: n_paths too large (>= 2^40)");
-  if (weights_dev && weights_stride != 0 && weights_stride < n_assets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_greeks_general: weights_stride must be 0 or >= n_assets");
-  if (corr_dev && corr_stride != 0 && corr_stride < n_assets * (n_assets - 1) / 2)
-    return fail(SMC_ERR_INVALID_ARGUMENT,
-                "smc_basket_greeks_general: corr_stride must be 0 or >= n_assets (n_assets - 1) / 2");
+  const BasketCall c{"smc_basket_greeks_general", contracts_dev, n_contracts, n_assets, timesteps, n_paths,
+                     mc_seed, ordinal_dev, ordinal0, math, normalization};
+  if (int32_t st = check_basket_call(c, "greeks_dev", greeks_dev)) return st;
+  if (int32_t st = check_basket_strides(c, weights_dev, weights_stride, corr_dev, corr_stride)) return st;
   if (n_contracts == 0) return SMC_OK;
-  size_t lds = 0;
-  const int mode = basket_greeks_general_mode(n_assets, n_paths, math, normalization, &lds);
-  BasketArgs a{};
-  a.contracts = contracts_dev;
-  a.B = n_contracts;
-  a.T = timesteps;
-  a.P = n_paths;
-  a.seed = mc_seed;
-  a.ordinal_dev = ordinal_dev;
-  a.ordinal0 = ordinal0;
-  a.normalize = normalization != SMC_NORM_RAW;
-  // A = 1 has no correlation entry: nothing to read, whatever the caller passed
-  const BasketGeneralArgs g{weights_dev, weights_stride, n_assets > 1 ? corr_dev : nullptr, corr_stride};
-  return (math & SMC_MATH_HW)
-             ? launch_basket_greeks_general<true>(n_assets, a, g, mode, lds, greeks_dev, sums_dev, as_stream(stream))
-             : launch_basket_greeks_general<false>(n_assets, a, g, mode, lds, greeks_dev, sums_dev, as_stream(stream));
+  const auto pick = [](auto A, auto HW, auto MODE) { return basket_greeks_general_kernel<A(), HW(), MODE()>; };
+  return launch_parked(c, kParkGreeksGeneral, as_stream(stream), pick, basket_args(c, nullptr),
+                       basket_general_args(c, weights_dev, weights_stride, corr_dev, corr_stride), greeks_dev, sums_dev);
 }
 
 const char* smc_basket_greeks_general_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
                                              int32_t normalization) {
-  size_t lds = 0;
-  if (timesteps <= 0) return "unsupported";
-  switch (basket_greeks_general_mode(n_assets, n_paths, math, normalization, &lds)) {
-    case kBPriceRaw: return "basket_greeks_general_kernel(raw)";
-    case kBPriceLds: return "basket_greeks_general_kernel(lds)";
-    case kBPriceReplay: return "basket_greeks_general_kernel(replay)";
-    default: return "unsupported";
-  }
+  return park_kernel_name(kParkGreeksGeneral, n_assets, timesteps, n_paths, math, normalization);
 }
 
 int32_t smc_basket_greeks_general_cols(int32_t n_assets) {
@@ -2949,46 +2727,25 @@ int32_t smc_basket_price_paths(const double* contracts_dev, const double* weight
                                int64_t n_contracts, int32_t n_assets, int32_t timesteps, int64_t n_paths,
                                uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
                                int32_t normalization, double* prices_dev, double* terminal_sum_dev, void* stream) {
-  if (!contracts_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: contracts_dev is NULL");
-  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: prices_dev is NULL");
-  if (n_assets < 1 || n_assets > kMaxAssets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: n_assets must be in 1..8");
-  if (math & ~(SMC_MATH_HW | SMC_PRICE_REPLAY))
-    return fail(SMC_ERR_INVALID_ARGUMENT,
-                "smc_basket_price_paths: bad math (0 or SMC_MATH_HW, optionally | SMC_PRICE_REPLAY)");
-  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: bad normalization");
-  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || timesteps <= 0 || n_paths <= 0)
-    return fail(SMC_ERR_INVALID_SHAPE,
-                "smc_basket_price_paths: need 0 <= n_contracts < 2^31, timesteps > 0, n_paths > 0");
-  if (n_paths >= (int64_t{1} << 40))
-    return fail(SMC_ERR_INVALID_SHAPE, "smc_basket_price_paths: n_paths too large (>= 2^40)");
-  if (weights_dev && weights_stride != 0 && weights_stride < n_assets)
-    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_basket_price_paths: weights_stride must be 0 or >= n_assets");
-  if (corr_dev && corr_stride != 0 && corr_stride < n_assets * (n_assets - 1) / 2)
-    return fail(SMC_ERR_INVALID_ARGUMENT,
-                "smc_basket_price_paths: corr_stride must be 0 or >= n_assets (n_assets - 1) / 2");
+  const BasketCall c{"smc_basket_price_paths", contracts_dev, n_contracts, n_assets, timesteps, n_paths,
+                     mc_seed, ordinal_dev, ordinal0, math, normalization};
+  if (int32_t st = check_basket_call(c, "prices_dev", prices_dev)) return st;
+  if (int32_t st = check_basket_strides(c, weights_dev, weights_stride, corr_dev, corr_stride)) return st;
   size_t lds = 0;
   int dates = 0;
   if (basket_path_plan(n_assets, timesteps, n_paths, math, normalization, &lds, &dates) < 0)
     return fail(SMC_ERR_INVALID_SHAPE,
                 "smc_basket_price_paths: n_assets * timesteps scales do not fit the LDS table (SMC_NORM_NORMALIZE)");
   if (n_contracts == 0) return SMC_OK;
-  BasketArgs a{};
-  a.contracts = contracts_dev;
-  a.B = n_contracts;
-  a.T = timesteps;
-  a.P = n_paths;
-  a.seed = mc_seed;
-  a.ordinal_dev = ordinal_dev;
-  a.ordinal0 = ordinal0;
-  a.normalize = normalization != SMC_NORM_RAW;
-  a.terminal_sum = terminal_sum_dev;
-  // A = 1 has no correlation entry: nothing to read, whatever the caller passed
-  const BasketGeneralArgs g{weights_dev, weights_stride, n_assets > 1 ? corr_dev : nullptr, corr_stride};
-  return (math & SMC_MATH_HW)
-             ? launch_basket_path<true>(n_assets, a, g, barriers_dev, lds, dates, prices_dev, as_stream(stream))
-             : launch_basket_path<false>(n_assets, a, g, barriers_dev, lds, dates, prices_dev, as_stream(stream));
+  const BasketArgs a = basket_args(c, terminal_sum_dev);
+  const BasketGeneralArgs g = basket_general_args(c, weights_dev, weights_stride, corr_dev, corr_stride);
+  const auto pick = [](auto A, auto HW, auto NORM) { return basket_path_kernel<A(), HW(), NORM()>; };
+  return with_variant(n_assets, math & SMC_MATH_HW, c.entry, [&](auto A, auto HW) {
+    return with_flag(a.normalize, [&](auto NORM) {
+      return launch_per_contract(pick(A, HW, NORM), "basket_path_kernel", c.B, lds, as_stream(stream), a, g,
+                                 barriers_dev, prices_dev, dates);
+    });
+  });
 }
 
 const char* smc_basket_price_paths_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
@@ -3004,3 +2761,4 @@ const char* smc_basket_price_paths_kernel(int32_t n_assets, int32_t timesteps, i
 
 #pragma GCC visibility pop
 }  // extern "C"
+
