@@ -1,0 +1,259 @@
+"""The ledger of training-kernel instantiations: every template instantiation the host code of csrc/gbm.hip
+(launch_engine<float>, launch_engine<double>) and csrc/basket.hip (launch_basket_k, launch_basket_resident_k) can
+select, written out literally, and the host rules that map a row of a reference test's case table to the one it
+runs.  tests/test_instantiation_ledger.py holds the ledger to the source text and the case tables to the ledger: the
+unit that can be wrong in this code base is the instantiation, so every reachable one has to have
+a case in the float64-reference files.  No GPU, no library: plain Python.
+
+A single-asset tuple is (kernel, dtype, scheme, math, store, variant):
+* kernel: the __global__ template's name;
+* dtype "f32" / "f64", scheme "log" / "simple", math "portable" / "hw" (rows_ref_kernel: "reference" /
+  "reference_hw", its HWN argument);
+* store: the STORE_ALL template argument as "ALL" / "TERMINAL"; for contract_kernel and queue_kernel the ALLROWS
+  argument as "ROWSUMS" / "NOSUMS" (their store mode is a run-time value);
+* variant: what the launch helper selects beside the macro's arguments (launch_wave_k: "T1" / "T2";
+  launch_resident_k: "T16" / "rolled" / "ONTHEFLY"; launch_packed_k: "T16" / "rolled"; SMC_SPLIT's ST argument:
+  "straight" / "split"; "" elsewhere).
+A basket tuple is (kernel, A, math, mode): basket_kernel's MODE as "fused" (0) / "split" (1, followed by
+basket_cf_kernel), basket_resident_kernel's STORE_ALL as "ALL" / "TERMINAL".
+"""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+from itertools import product
+
+SCHEMES = ("log", "simple")
+MATHS = ("portable", "hw")
+STORES = ("ALL", "TERMINAL")
+SUMS = ("ROWSUMS", "NOSUMS")
+REF_MATHS = ("reference", "reference_hw")
+VARIANTS = {"wave_kernel": ("T1", "T2"), "resident_kernel": ("T16", "rolled", "ONTHEFLY"),
+            "packed_kernel": ("T16", "rolled")}
+# what smc_train_targets_kernel reports for the kernel
+QUERY_NAME = {"wave_kernel": "wave_kernel", "resident_kernel": "resident_kernel", "packed_kernel": "packed_kernel",
+              "paths_kernel": "paths_kernel+cf_kernel", "rows_kernel": "rows_kernel+cf_kernel",
+              "rows_ref_kernel": "rows_ref_kernel+cf_kernel", "contract_kernel": "contract_kernel",
+              "queue_kernel": "queue_kernel"}
+
+ALL_GBM: frozenset[tuple] = frozenset(
+    # SMC_WAVE x launch_wave_k's a.T == 1 ? <..., 1> : <..., 2>
+    [("wave_kernel", "f32", s, m, st, v) for s, m, st, v in product(SCHEMES, MATHS, STORES, VARIANTS["wave_kernel"])]
+    # SMC_RES x launch_resident_k's T == 16 ? T16 : (!normalize && W == 1) ? ONTHEFLY : rolled
+    + [("resident_kernel", "f32", s, m, st, v)
+       for s, m, st, v in product(SCHEMES, MATHS, STORES, VARIANTS["resident_kernel"])]
+    # SMC_PACK x launch_packed_k's T == 16 ? T16 : rolled
+    + [("packed_kernel", "f32", s, m, st, v) for s, m, st, v in product(SCHEMES, MATHS, STORES, VARIANTS["packed_kernel"])]
+    # SMC_SPLIT: the straight form with either store, the other form with STORE_ALL = true only
+    + [("paths_kernel", "f32", s, m, st, "straight") for s, m, st in product(SCHEMES, MATHS, STORES)]
+    + [("paths_kernel", "f32", s, m, "ALL", "split") for s, m in product(SCHEMES, MATHS)]
+    # SMC_ROWS: the HW lines under if constexpr (sizeof(Real) == 4)
+    + [("rows_kernel", "f32", s, m, st, "") for s, m, st in product(SCHEMES, MATHS, STORES)]
+    + [("rows_kernel", "f64", s, "portable", st, "") for s, st in product(SCHEMES, STORES)]
+    # SMC_LAUNCH x launch_engine_k's a.slices > 1 ? queue_kernel : contract_kernel
+    + [(k, "f32", s, m, rs, "") for k, s, m, rs in product(("contract_kernel", "queue_kernel"), SCHEMES, MATHS, SUMS)]
+    + [(k, "f64", s, "portable", rs, "") for k, s, rs in product(("contract_kernel", "queue_kernel"), SCHEMES, SUMS)]
+    # the eight launch_rows_ref_k<LOG_EULER, STORE_ALL, HWN> calls
+    + [("rows_ref_kernel", "f32", s, m, st, "") for s, m, st in product(SCHEMES, REF_MATHS, STORES)])
+
+MAX_ASSETS = 8
+BASKET_MODES = ("fused", "split")
+ALL_BASKET: frozenset[tuple] = frozenset(
+    # with_variant (with_assets: A = 1..8, with_flag: HW) x launch_basket_k's MODE, launch_basket_resident_k's store_all
+    [("basket_kernel", A, m, mode) for A, m, mode in product(range(1, MAX_ASSETS + 1), MATHS, BASKET_MODES)]
+    + [("basket_resident_kernel", A, m, st) for A, m, st in product(range(1, MAX_ASSETS + 1), MATHS, STORES)])
+
+
+# ---- the host rules of csrc/gbm.hip ----------------------------------------------------------------------------------
+K_CHUNK, K_SLICE_CHUNKS, K_ROW_BLOCK = 2048, 4, 16
+K_RES_CHUNK, K_RES_MAX_CHUNKS, K_RES_MAX_T = 4096, 16, 1 << 16
+K_PACK_MIN_P, K_PACK_MAX_P = 256, 2048
+K_WAVE_LANE_PATHS, K_WAVE_CHUNK, K_WAVE_MAX_T = 16, 1024, 2
+
+
+def path_pitch(n_paths: int, f64: bool = False) -> int:
+    """smc_path_pitch: the row rounded up to 4 KiB, then to an odd multiple of 4 KiB."""
+    unit = 4096 // (8 if f64 else 4)
+    units = -(-n_paths // unit)
+    return (units + 1 - units % 2) * unit
+
+
+def slices_for(P: int, sliced: bool) -> int:
+    if not sliced:
+        return 1
+    return -(-(-(-P // K_CHUNK)) // K_SLICE_CHUNKS)
+
+
+@dataclass(frozen=True)
+class Args:
+    """What the *_ok predicates read of EngineArgs in a smc_train_targets call (simulate and targets are set,
+    res_slices is 0: whole contracts per resident workgroup)."""
+    T: int
+    N: int
+    P: int
+    pitch: int
+    normalize: bool
+    all_rows: bool
+    slices: int
+    f32: bool
+
+
+def _pitch_ok(a: Args) -> bool:
+    return a.pitch == 0 or (a.pitch % 4 == 0 and a.pitch >= a.P)
+
+
+def wave_ok(a: Args) -> bool:
+    return (a.f32 and not a.normalize and not a.all_rows and a.slices <= 1 and 1 <= a.T <= K_WAVE_MAX_T
+            and a.P % K_WAVE_CHUNK == 0 and a.N >= K_WAVE_LANE_PATHS and a.N % K_WAVE_LANE_PATHS == 0
+            and K_WAVE_CHUNK % a.N == 0 and _pitch_ok(a))
+
+
+def resident_ok(a: Args) -> bool:
+    return (a.f32 and not a.all_rows and a.slices <= 1 and 1 <= a.T <= K_RES_MAX_T and a.P % K_RES_CHUNK == 0
+            and a.P // K_RES_CHUNK <= K_RES_MAX_CHUNKS and 4 <= a.N <= 1024 and K_RES_CHUNK % a.N == 0 and _pitch_ok(a))
+
+
+def packed_ok(a: Args) -> bool:
+    return (a.f32 and not a.all_rows and a.slices <= 1 and 1 <= a.T <= K_RES_MAX_T
+            and K_PACK_MIN_P <= a.P <= K_PACK_MAX_P and K_RES_CHUNK % a.P == 0 and a.N >= 4 and a.N % 4 == 0
+            and a.P % a.N == 0 and _pitch_ok(a))
+
+
+def _padding(a: Args) -> int:
+    return (a.pitch or a.P) - a.P
+
+
+def split_ok(a: Args) -> bool:
+    return a.f32 and not a.all_rows and a.slices <= 1 and _padding(a) >= (a.P & 1) + 2
+
+
+def rows_ok(a: Args) -> bool:
+    return (not a.all_rows and a.slices <= 1 and a.T >= 1 and a.P % K_CHUNK == 0
+            and _padding(a) >= ((a.P & 1) + 2 if a.f32 else 1))
+
+
+def ref_ok(a: Args) -> bool:
+    return not a.all_rows and a.slices <= 1 and a.T >= 1 and _padding(a) >= (a.P & 1) + 2
+
+
+def select(a: Args, reference_typing: bool = False) -> tuple[str, str]:
+    """(kernel, variant) by launch_engine's order of precedence."""
+    if reference_typing:
+        assert a.f32 and ref_ok(a), "SMC_MATH_REF needs f32, whole contracts and a padded pitch"
+        return "rows_ref_kernel", ""
+    if a.f32:
+        if wave_ok(a):
+            return "wave_kernel", "T1" if a.T == 1 else "T2"
+        if resident_ok(a):
+            return "resident_kernel", "T16" if a.T == K_ROW_BLOCK else "rolled" if a.normalize else "ONTHEFLY"
+        if packed_ok(a):
+            return "packed_kernel", "T16" if a.T == K_ROW_BLOCK else "rolled"
+        straight = a.T == K_ROW_BLOCK and a.P % K_CHUNK == 0
+        if split_ok(a) and (straight or not rows_ok(a)):
+            return "paths_kernel", "straight" if straight else "split"
+    if rows_ok(a):
+        return "rows_kernel", ""
+    return ("queue_kernel" if a.slices > 1 else "contract_kernel"), ""
+
+
+def gbm_instantiation(*, dtype: str, T: int, N: int, M: int, scheme: str, normalize: bool, store: str, pitch: int,
+                      sliced: bool, with_rowsum: bool, math: str) -> tuple:
+    P = N * M
+    a = Args(T, N, P, pitch, normalize, with_rowsum, slices_for(P, sliced), dtype == "f32")
+    kernel, variant = select(a, math in REF_MATHS)
+    if kernel in ("contract_kernel", "queue_kernel"):
+        store = "ROWSUMS" if with_rowsum else "NOSUMS"
+    elif (kernel, variant) == ("paths_kernel", "split"):
+        store = "ALL"  # SMC_SPLIT: (!ST || sa == SA), the one instantiation takes either run-time store mode
+    return kernel, dtype, scheme, math, store, variant
+
+
+# ---- the case tables -------------------------------------------------------------------------------------------------
+_SCHEME = {0: "log", 1: "simple"}
+_STORE = {2: "ALL", 1: "TERMINAL"}  # SMC_STORE_ALL, SMC_STORE_TERMINAL
+
+
+def instantiation_of(table: str, case: tuple, math: str, with_rowsum: bool = False) -> tuple:
+    """The instantiation one run of a case row reaches.  table: "train" (TRAIN_CASES of test_gpu_gbm_reference.py),
+    "ref" (REF_CASES), "f64" (F64_TRAIN_CASES of test_gpu_gbm_typing_reference.py), "basket split" (SPLIT_CASES with
+    math and with_rowsum = the terminal sums kept) or "basket resident" (RESIDENT_CASES with math and
+    with_rowsum = every row stored)."""
+    if table == "train":
+        _, _, T, N, M, scheme, normalize, store, padded, sliced = case
+        return gbm_instantiation(dtype="f32", T=T, N=N, M=M, scheme=_SCHEME[scheme], normalize=normalize,
+                                 store=_STORE[store], pitch=path_pitch(N * M) if padded else N * M, sliced=sliced,
+                                 with_rowsum=with_rowsum, math=math)
+    if table == "ref":
+        _, T, N, M, scheme, normalize, store = case
+        return gbm_instantiation(dtype="f32", T=T, N=N, M=M, scheme=_SCHEME[scheme], normalize=normalize,
+                                 store=_STORE[store], pitch=path_pitch(N * M + 4), sliced=False, with_rowsum=False,
+                                 math=math)
+    if table == "f64":
+        _, _, T, N, M, scheme, normalize, store, padded, sliced, _ = case
+        return gbm_instantiation(dtype="f64", T=T, N=N, M=M, scheme=_SCHEME[scheme], normalize=normalize,
+                                 store=_STORE[store], pitch=path_pitch(N * M, True) if padded else N * M,
+                                 sliced=sliced, with_rowsum=with_rowsum, math=math)
+    if table == "basket split":
+        A, T, N, M, _ = case
+        assert basket_kernel_of(A, T, N, M, resident=False) == "basket_kernel"
+        return "basket_kernel", A, math, "split" if with_rowsum else "fused"
+    assert table == "basket resident", table
+    A, N, M, _ = case
+    assert basket_kernel_of(A, 16, N, M, resident=True) == "basket_resident_kernel"
+    return "basket_resident_kernel", A, math, "ALL" if with_rowsum else "TERMINAL"
+
+
+def runs_of(table: str, case: tuple) -> list[tuple]:
+    """Every instantiation the test of the table runs for the case row: both math modes where the kernel has both, and
+    contract_kernel / queue_kernel with and without row sums where the test asks for both."""
+    if table == "train":
+        sums = (False, True) if case[0] in ("contract_kernel", "queue_kernel") else (False,)
+        return [instantiation_of(table, case, m, rs) for m in MATHS for rs in sums]
+    if table == "ref":
+        return [instantiation_of(table, case, m) for m in REF_MATHS]
+    if table == "f64":
+        return [instantiation_of(table, case, "portable", rs) for rs in ((False, True) if case[-1] else (False,))]
+    return [instantiation_of(table, case, m, flag) for m in MATHS for flag in (False, True)]
+
+
+def table_kernel(table: str, case: tuple) -> str:
+    """The kernel name the case row states (what its GPU test asserts against the library's name query)."""
+    return {"train": lambda: case[0], "f64": lambda: case[0], "ref": lambda: "rows_ref_kernel+cf_kernel",
+            "basket split": lambda: "basket_kernel", "basket resident": lambda: "basket_resident_kernel"}[table]()
+
+
+def derived_kernel(table: str, case: tuple) -> str:
+    """The kernel name the host rules give for the case row's plain run, in the name query's words."""
+    inst = runs_of(table, case)[0]
+    return QUERY_NAME.get(inst[0], inst[0])
+
+
+# ---- the host rules of csrc/basket.hip -------------------------------------------------------------------------------
+K_R_CHUNK, K_R_MAX_SLICES, K_R_THREADS, K_R_WAVES, K_R_TABLE = 4096, 32, 1024, 16, 64
+BASKET_RES_LDS_LIMIT = 160 * 1024
+
+
+def basket_resident_lds_bytes(A: int) -> int:
+    """basket_resident_lds_bytes: terminal slots [A][1024] of 16 B, part [4096] and wsum [16][8] and 16 more f64, two
+    coefficient tables of 64 and two slots of [2 A + A^2] f32."""
+    return A * K_R_THREADS * 16 + (4096 + K_R_WAVES * MAX_ASSETS + 16) * 8 + (2 * K_R_TABLE + 2) * (2 * A + A * A) * 4
+
+
+def basket_res_slices(A: int, T: int, N: int, M: int) -> int:
+    P = N * M
+    if T != K_ROW_BLOCK or N < 4 or N > 2048 or N % 4 or K_R_CHUNK % N or P % K_R_CHUNK:
+        return 0
+    W = P // K_R_CHUNK
+    return 0 if W < 1 or W > K_R_MAX_SLICES or basket_resident_lds_bytes(A) > BASKET_RES_LDS_LIMIT else W
+
+
+def basket_kernel_of(A: int, T: int, N: int, M: int, *, resident: bool) -> str:
+    return "basket_resident_kernel" if resident and basket_res_slices(A, T, N, M) > 0 else "basket_kernel"
+
+
+# Instantiations the build contains and no call can reach, each with the host rule that keeps it out.
+UNREACHABLE: dict[tuple, str] = {
+    ("basket_resident_kernel", A, m, st):
+        f"basket_res_slices returns 0: basket_resident_lds_bytes({A}, N) = {basket_resident_lds_bytes(A)} > 160 KiB for "
+        "every N, so smc_basket_train_targets launches basket_kernel"
+    for A, m, st in product((7, 8), MATHS, STORES)}

@@ -185,6 +185,100 @@ def test_wrong_readings_leave_the_bound() -> None:
     assert not survivors, survivors
 
 
+# ---- wrong readings of the cells the instantiation ledger added ------------------------------------------------------
+# What an instantiation of tests/helpers/instantiations.py could do wrong that the thirteen readings above do not say:
+# * resident_kernel<.., ONTHEFLY> is the RAW kernel (pay_raw(.., 1.0)): it must not apply NORMALIZE's scale;
+# * a STORE_TERMINAL instantiation hands out one row: it must be row T - 1, not T - 2;
+# * the paths_kernel of ragged shapes keeps the f64 terminal sum behind one padding element where P is odd: the lane
+#   that straddles P simulates path P as well (its draws are made and dropped) and must not add it to the sum.
+# Each is put in the reference's place for the outputs it touches alone, against the unchanged bound, contract by
+# contract.  The condition: in every case where the reading applies it leaves the bound, and the first two do so on
+# every contract but the flat one (whose bounds are zero) and, for the reading that shows in the targets only, but
+# those whose reference put is zero on every path (their target is zero under either reading: nothing is there to
+# see).  The third adds one path to a sum of P: that is visible where the path is larger than the sum's bound, which
+# it is for the contracts of moderate volatility (factors of 10 to 3000) and is not for those with v sqrt(T) of 3 and
+# more, where a typical path is a vanishing part of a sum that a few large ones carry (factors down to 0.03).  The
+# test prints on how many contracts each reading shows.
+CELL_MUTANTS = ("RAW targets on the NORMALIZE scale", "terminal row taken as row T - 2",
+                "odd-P padding element in the terminal sum")
+CELL_CASES = [*MUTANT_CASES, (7, 693, 0, True)]  # and the ragged split pair's own shape, in log-Euler
+
+
+def _per_contract(got: np.ndarray, want: np.ndarray, bound: np.ndarray) -> np.ndarray:
+    """[B]: the largest |got - want| / bound of each contract (complex: of the real and the imaginary parts)."""
+    if np.iscomplexobj(want):
+        return np.maximum(_per_contract(got.real, want.real, bound), _per_contract(got.imag, want.imag, bound))
+    B = want.shape[0]
+    return np.array([gref.share_used(got[b], want[b], bound[b]) for b in range(B)])
+
+
+def _targets_given_sum(rows: np.ndarray, good: gref.GbmRef, tot: np.ndarray, T: int, N: int, M: int) -> np.ndarray:
+    """NORMALIZE targets of the reference's terminal row scaled by F_T / (tot / P)."""
+    F, eF = gref.forwards(rows, T)
+    xs, dxs = gref.scaled(good.xT, good.dxT, tot, good.rowsum_bound[:, -1], F[:, -1], eF[:, -1])
+    df, edf = gref.discount(rows)
+    put, dput = gref.payoff(1.0, gref.fields(rows)[1][:, None], xs, dxs, df[:, None], edf[:, None])
+    return gref.targets(put, dput, N, M)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def _cell_mutant_factors() -> dict[str, dict[tuple, np.ndarray]]:
+    """reading -> case -> [B] factor by which it leaves the bound per contract (NaN: the contract cannot show it)."""
+    oracle = _oracle()
+    out: dict[str, dict[tuple, np.ndarray]] = {name: {} for name in CELL_MUTANTS}
+    for case in CELL_CASES:
+        T, P, scheme, normalize = case
+        N, M = SHAPE[P]
+        rows, _ = case_rows(scheme, normalize)
+        good = _reference(T, P, scheme, normalize)
+        got = _kernel_mode(T, P, scheme, normalize)
+        assert_within(shares(got, good), case)
+        K = gref.fields(rows)[1]
+        flat = np.arange(rows.shape[0]) == FLAT
+        if not normalize:
+            scale = good.xT.shape[-1] * gref.forwards(rows, T)[0][:, -1] / good.rowsum[:, -1]  # F_T / mean x_T
+            blind = flat | np.all(np.maximum(K[:, None] - good.xT, 0.0) == 0.0, axis=1) \
+                | np.all(np.maximum(K[:, None] - good.xT * scale[:, None], 0.0) == 0.0, axis=1)
+            wrong = _targets_given_sum(rows, good, good.rowsum[:, -1], T, N, M)
+            f = _per_contract(got["targets"], wrong, good.targets_bound)
+            out[CELL_MUTANTS[0]][case] = np.where(blind, np.nan, f)
+        if T >= 2:
+            f = _per_contract(got["paths"][:, -1], good.x[:, T - 2], good.dxT)
+            out[CELL_MUTANTS[1]][case] = np.where(flat, np.nan, f)
+        if P % 2 and T >= 3:
+            words = gref.stream_words(oracle, rows.shape[0], T, P + 1, SEED, ORD0)
+            assert words.shape[1] == -(-P // 4)  # path P belongs to the last group of the P paths
+            z, rad = gref.normals(words, T, P + 1)
+            x1, _ = gref.paths(rows, T, z, rad, gref.PORTABLE, scheme)
+            np.testing.assert_array_equal(x1[:, :, :P], good.x)
+            tot = good.rowsum[:, -1] + x1[:, -1, P]
+            f = _per_contract(got["row sums"][:, -1], tot, good.rowsum_bound[:, -1])
+            if normalize:
+                wrong = _targets_given_sum(rows, good, tot, T, N, M)
+                f = np.maximum(f, _per_contract(got["targets"], wrong, good.targets_bound))
+            out[CELL_MUTANTS[2]][case] = np.where(flat, np.nan, f)
+    return out
+
+
+def test_wrong_readings_of_the_new_cells_leave_the_bound() -> None:
+    factors = _cell_mutant_factors()
+    for name in CELL_MUTANTS:
+        cases = factors[name]
+        assert cases, name
+        seen = np.concatenate(list(cases.values()))
+        print(f"{name}: over {len(cases)} cases, the factor by which it leaves the bound per contract "
+              f"{np.nanmin(seen):.3g} .. {np.nanmax(seen):.3g}; contracts that cannot show it "
+              f"{sorted({int(b) for f in cases.values() for b in np.flatnonzero(np.isnan(f))})}")
+        for case, f in cases.items():
+            able = f[~np.isnan(f)]
+            assert able.size >= 8, (name, case)  # the exemptions stay exceptions
+            print(f"  {case}: leaves the bound on {int(np.sum(able > 1.0))} of {able.size} contracts, "
+                  f"factor {able.min():.3g} .. {able.max():.3g}")
+            assert able.max() > 1.0, (name, case, f.tolist())  # in every case, not only somewhere on the case set
+            if name != CELL_MUTANTS[2]:
+                assert np.all(able > 1.0), (name, case, f.tolist())
+
+
 # ---- the reference against closed forms of its own -------------------------------------------------------------------
 def test_reference_put_is_blacks_put(oracle) -> None:
     rows = gr.contracts(8)

@@ -46,29 +46,32 @@ def _reference(rows: np.ndarray, A: int, T: int, P: int, math: str, **kw) -> br.
 
 
 def _train(rows: np.ndarray, A: int, T: int, N: int, M: int, math: str, *, resident: bool, store: bool,
-           pitch: int = 0) -> tuple[np.ndarray | None, np.ndarray, np.ndarray]:
-    """(stored paths [B, A, T, pitch or P] or None, terminal sums, targets) of one training call."""
+           pitch: int = 0, keep_sums: bool = True) -> tuple[np.ndarray | None, np.ndarray | None, np.ndarray]:
+    """(stored paths [B, A, T, pitch or P] or None, terminal sums or None, targets) of one training call.
+    keep_sums = False passes no terminal-sum buffer: the split pair's kernel then runs fused (basket_kernel<A, HW, 0>)."""
     cfg = BasketConfig(n_assets=A, timesteps=T, network_size=N, batches_per_mc_run=M, mc_seed=SEED, math=math)
     B = rows.shape[0]
     cd = torch.tensor(rows, dtype=torch.float64, device=DEV)
     paths = poisoned((B, A, T, pitch or N * M), torch.float32, DEV) if store else None
-    tsum = poisoned((B, A), torch.float64, DEV)
+    tsum = poisoned((B, A), torch.float64, DEV) if keep_sums else None
     tg = poisoned((B, N), torch.complex64, DEV)
     basket_targets(cd, cfg, ordinal0=ORD0, paths=paths, terminal_sum=tsum, targets=tg, pitch=pitch, resident=resident)
     torch.cuda.synchronize()
-    return (paths.cpu().numpy() if store else None), tsum.cpu().numpy(), tg.cpu().numpy()
+    return (paths.cpu().numpy() if store else None), (tsum.cpu().numpy() if keep_sums else None), tg.cpu().numpy()
 
 
 def _check_training(got: tuple, ref: br.BasketRef, label: str) -> None:
     paths, tsum, tg = got
     P = ref.xT.shape[-1]
-    used = {"sums": br.share_used(tsum, ref.tot, ref.tot_bound),
-            "targets": br.complex_share_used(tg, ref.targets, ref.targets_bound)}
+    used = {"targets": br.complex_share_used(tg, ref.targets, ref.targets_bound)}
+    if tsum is not None:
+        assert not np.isnan(tsum).any(), label
+        used["sums"] = br.share_used(tsum, ref.tot, ref.tot_bound)
     if paths is not None:
         assert not np.isnan(paths[..., :P]).any(), label
         assert np.isnan(paths[..., P:]).all(), f"{label}: the padding of the pitch was written"
         used["paths"] = br.share_used(paths[..., :P], ref.x, ref.paths_bound)
-    assert not np.isnan(tsum).any() and not np.isnan(tg).any(), label
+    assert not np.isnan(tg).any(), label
     print(f"{label}: share of the bound used " + ", ".join(f"{k} {v:.3f}" for k, v in used.items()))
     assert max(used.values()) < 1.0, (label, used)
 
@@ -78,11 +81,19 @@ def _name(A: int, T: int, N: int, M: int, resident: bool) -> str:
 
 
 # ---- basket_kernel + basket_cf_kernel --------------------------------------------------------------------------------
-@pytest.mark.parametrize("A,T,N,M,padded", [(1, 5, 64, 32, False), (2, 16, 64, 32, False), (3, 16, 64, 32, True),
-                                            (5, 1, 64, 32, False), (7, 3, 64, 32, False), (8, 5, 64, 32, False),
-                                            (4, 16, 64, 64, False)])
+# (A, T, N, M, padded pitch): basket_kernel<A, HW, MODE> is instantiated per asset count with unrolled Cholesky and
+# driver code, so every A = 1 .. 8 runs, in both math modes, split (MODE 1 + basket_cf_kernel: the terminal sums kept)
+# and fused (MODE 0); tests/test_instantiation_ledger.py holds this table to the ledger of instantiations
+SPLIT_CASES = [(1, 5, 64, 32, False), (2, 16, 64, 32, False), (3, 16, 64, 32, True), (5, 1, 64, 32, False),
+               (7, 3, 64, 32, False), (8, 5, 64, 32, False), (4, 16, 64, 64, False),
+               (1, 3, 64, 32, False), (2, 3, 64, 32, False), (3, 3, 64, 32, False), (4, 3, 64, 32, False),
+               (5, 3, 64, 32, False), (6, 3, 64, 32, False), (8, 3, 64, 32, False)]
+
+
+@pytest.mark.parametrize("A,T,N,M,padded", SPLIT_CASES)
 def test_split_pair_stored_paths_sums_and_targets(A, T, N, M, padded) -> None:
     assert _name(A, T, N, M, False) == "basket_kernel+basket_cf_kernel"
+    assert _lib.lib().smc_basket_train_targets_kernel(A, T, N, M, 0, 0) == b"basket_kernel"  # no sums kept: fused
     rows = _sobol_rows(A, 6)
     pitch = int(_lib.lib().smc_path_pitch(N * M, 0)) if padded else 0
     assert not padded or pitch > N * M
@@ -90,10 +101,17 @@ def test_split_pair_stored_paths_sums_and_targets(A, T, N, M, padded) -> None:
         ref = _reference(rows, A, T, N * M, math, N=N, M=M, keep_paths=True)
         got = _train(rows, A, T, N, M, math, resident=False, store=True, pitch=pitch)
         _check_training(got, ref, f"split pair A {A} T {T} P {N * M} {math}")
+        got = _train(rows, A, T, N, M, math, resident=False, store=True, pitch=pitch, keep_sums=False)
+        _check_training(got, ref, f"fused A {A} T {T} P {N * M} {math}")
 
 
 # ---- basket_resident_kernel ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("A,N,M,W", [(4, 256, 16, 1), (6, 256, 32, 2), (3, 2048, 6, 3)])
+# (A, N, M, W): every asset count the resident kernel's LDS budget admits (A <= 6) at one workgroup per contract
+RESIDENT_CASES = [(4, 256, 16, 1), (6, 256, 32, 2), (3, 2048, 6, 3),
+                  (1, 256, 16, 1), (2, 256, 16, 1), (3, 256, 16, 1), (5, 256, 16, 1), (6, 256, 16, 1)]
+
+
+@pytest.mark.parametrize("A,N,M,W", RESIDENT_CASES)
 def test_resident_kernel_stored_and_terminal_only(A, N, M, W) -> None:
     T, B = 16, 4
     assert _name(A, T, N, M, True) == "basket_resident_kernel" and N * M == W * 4096

@@ -8,7 +8,9 @@ kernel mode (tests/test_gpu_engine.py), which tests/test_gbm_reference.py holds 
 portable cases here assert that the stored paths use exactly the share of the bound the oracle's kernel mode uses,
 which ties the two files.
 
-Each case asserts the name of the kernel it means to reach.  The contracts are those of the CPU sweep
+Each case asserts the name of the kernel it means to reach, and TRAIN_CASES holds a row for every template
+instantiation of the training kernels that launch_engine<float> can select (tests/helpers/instantiations.py, held to
+the dispatch's text and to this table by tests/test_instantiation_ledger.py).  The contracts are those of the CPU sweep
 (tests/test_gbm_reference.case_rows: Sobol-drawn rows in the default bounds and the hand-built ones)."""
 
 from __future__ import annotations
@@ -33,7 +35,7 @@ ORD0 = 3
 MATHS = {"portable": (gref.PORTABLE, 0), "hw": (gref.HW, _lib.MATH_HW)}
 
 
-@functools.lru_cache(maxsize=4)
+@functools.lru_cache(maxsize=8)
 def _ref(B: int, T: int, P: int, scheme: int, normalize: bool, math: str, N: int = 0, M: int = 0, bars: bool = False,
          keep_paths: bool = False, ordinal0: int = ORD0) -> gref.GbmRef:
     """The reference of the first B case rows, once per shape."""
@@ -88,33 +90,83 @@ def _kernel_mode_paths_share(B: int, T: int, P: int, scheme: int, ref: gref.GbmR
     return gref.share_used(kp, ref.x, ref.dx) if store == _lib.STORE_ALL else gref.share_used(term, ref.xT, ref.dxT)
 
 
-ALL, LOG, SIMPLE = _lib.STORE_ALL, gref.LOG_EULER, gref.SIMPLE_EULER
-# (kernel, B, T, N, M, scheme, normalize, padded pitch, sliced)
+ALL, TERMINAL, LOG, SIMPLE = _lib.STORE_ALL, _lib.STORE_TERMINAL, gref.LOG_EULER, gref.SIMPLE_EULER
+# (kernel, B, T, N, M, scheme, normalize, store, padded pitch, sliced).  tests/test_instantiation_ledger.py holds this
+# table, by the host rules of csrc/gbm.hip, to the ledger of instantiations launch_engine<float> can select: the rows
+# below "one row per instantiation" are the smallest shapes that select each one the rows above do not reach.
 TRAIN_CASES = [
-    ("resident_kernel", 12, 16, 64, 64, LOG, True, True, False),            # straight-line 16-row block
-    ("resident_kernel", 12, 16, 64, 64, SIMPLE, True, True, False),         # ... its simple-Euler instantiation
-    ("resident_kernel", 12, 5, 64, 64, LOG, True, True, False),             # rolled rows, odd T: the tail
-    ("resident_kernel", 12, 20, 64, 64, LOG, True, True, False),            # rolled rows, T > 16
-    ("resident_kernel", 3, 16, 512, 96, LOG, True, True, False),            # 12 chunks: registers beyond LDS
-    ("packed_kernel", 12, 16, 64, 8, LOG, True, True, False),               # P = 512
-    ("packed_kernel", 12, 5, 64, 32, LOG, False, True, False),              # P = 2048, odd T, RAW
-    ("packed_kernel", 12, 5, 64, 32, SIMPLE, True, True, False),            # ... in simple Euler
-    ("packed_kernel", 12, 1, 16, 64, LOG, True, True, False),               # P = 1024, T = 1: the stream span
-    ("wave_kernel", 12, 1, 16, 64, LOG, False, True, False),                # T = 1, N = 16, P = 1024
-    ("wave_kernel", 12, 2, 64, 64, LOG, False, True, False),                # T = 2, N = 64, P = 4096
-    ("wave_kernel", 12, 2, 64, 64, SIMPLE, False, True, False),             # ... in simple Euler
-    ("paths_kernel+cf_kernel", 12, 16, 1000, 4, LOG, True, True, False),    # the split pair, straight, padded pitch
-    ("rows_kernel+cf_kernel", 12, 17, 2048, 2, LOG, True, True, False),     # odd T beyond one row block, N > 1024
-    ("rows_kernel+cf_kernel", 12, 3, 64, 96, LOG, True, True, False),       # P = 6144
-    ("contract_kernel", 12, 7, 99, 7, SIMPLE, True, False, False),          # ragged P = 693
-    ("contract_kernel", 12, 20, 100, 30, SIMPLE, True, False, False),       # P = 3000, row-block replay
-    ("contract_kernel", 12, 7, 99, 7, LOG, True, False, False),             # ... the odd tail in log-Euler
-    ("queue_kernel", 12, 4, 99, 101, LOG, True, False, True),               # sliced contracts: P = 9999 > 8192
+    ("resident_kernel", 12, 16, 64, 64, LOG, True, ALL, True, False),            # straight-line 16-row block
+    ("resident_kernel", 12, 16, 64, 64, SIMPLE, True, ALL, True, False),         # ... its simple-Euler instantiation
+    ("resident_kernel", 12, 5, 64, 64, LOG, True, ALL, True, False),             # rolled rows, odd T: the tail
+    ("resident_kernel", 12, 20, 64, 64, LOG, True, ALL, True, False),            # rolled rows, T > 16
+    ("resident_kernel", 3, 16, 512, 96, LOG, True, ALL, True, False),            # 12 chunks: registers beyond LDS
+    ("packed_kernel", 12, 16, 64, 8, LOG, True, ALL, True, False),               # P = 512
+    ("packed_kernel", 12, 5, 64, 32, LOG, False, ALL, True, False),              # P = 2048, odd T, RAW
+    ("packed_kernel", 12, 5, 64, 32, SIMPLE, True, ALL, True, False),            # ... in simple Euler
+    ("packed_kernel", 12, 1, 16, 64, LOG, True, ALL, True, False),               # P = 1024, T = 1: the stream span
+    ("wave_kernel", 12, 1, 16, 64, LOG, False, ALL, True, False),                # T = 1, N = 16, P = 1024
+    ("wave_kernel", 12, 2, 64, 64, LOG, False, ALL, True, False),                # T = 2, N = 64, P = 4096
+    ("wave_kernel", 12, 2, 64, 64, SIMPLE, False, ALL, True, False),             # ... in simple Euler
+    ("paths_kernel+cf_kernel", 12, 16, 1000, 4, LOG, True, ALL, True, False),    # the split pair, P = 4000: not straight
+    ("rows_kernel+cf_kernel", 12, 17, 2048, 2, LOG, True, ALL, True, False),     # odd T beyond one row block, N > 1024
+    ("rows_kernel+cf_kernel", 12, 3, 64, 96, LOG, True, ALL, True, False),       # P = 6144
+    ("contract_kernel", 12, 7, 99, 7, SIMPLE, True, ALL, False, False),          # ragged P = 693
+    ("contract_kernel", 12, 20, 100, 30, SIMPLE, True, ALL, False, False),       # P = 3000, row-block replay
+    ("contract_kernel", 12, 7, 99, 7, LOG, True, ALL, False, False),             # ... the odd tail in log-Euler
+    ("queue_kernel", 12, 4, 99, 101, LOG, True, ALL, False, True),               # sliced contracts: P = 9999 > 8192
+    # ---- one row per instantiation ----
+    # resident_kernel<.., T16>, <.., rolled> and <.., ONTHEFLY> (RAW, whole contracts, T != 16; T >= 3, or RAW goes
+    # to wave_kernel) at P = 4096
+    ("resident_kernel", 12, 16, 64, 64, LOG, True, TERMINAL, True, False),
+    ("resident_kernel", 12, 16, 64, 64, SIMPLE, True, TERMINAL, True, False),
+    ("resident_kernel", 12, 5, 64, 64, LOG, True, TERMINAL, True, False),
+    ("resident_kernel", 12, 5, 64, 64, SIMPLE, True, ALL, True, False),
+    ("resident_kernel", 12, 5, 64, 64, SIMPLE, True, TERMINAL, True, False),
+    ("resident_kernel", 12, 5, 64, 64, LOG, False, ALL, True, False),
+    ("resident_kernel", 12, 5, 64, 64, LOG, False, TERMINAL, True, False),
+    ("resident_kernel", 12, 5, 64, 64, SIMPLE, False, ALL, True, False),
+    ("resident_kernel", 12, 5, 64, 64, SIMPLE, False, TERMINAL, True, False),
+    # packed_kernel<.., T16> and <.., rolled> at P = 512 (eight contracts per workgroup), RAW on the T16 simple rows
+    ("packed_kernel", 12, 16, 64, 8, LOG, True, TERMINAL, True, False),
+    ("packed_kernel", 12, 16, 64, 8, SIMPLE, False, ALL, True, False),
+    ("packed_kernel", 12, 16, 64, 8, SIMPLE, False, TERMINAL, True, False),
+    ("packed_kernel", 12, 5, 64, 8, LOG, True, TERMINAL, True, False),
+    ("packed_kernel", 12, 5, 64, 8, SIMPLE, True, TERMINAL, True, False),
+    # wave_kernel<.., 1> and <.., 2> at P = 1024
+    ("wave_kernel", 12, 1, 16, 64, LOG, False, TERMINAL, True, False),
+    ("wave_kernel", 12, 1, 16, 64, SIMPLE, False, ALL, True, False),
+    ("wave_kernel", 12, 1, 16, 64, SIMPLE, False, TERMINAL, True, False),
+    ("wave_kernel", 12, 2, 16, 64, LOG, False, TERMINAL, True, False),
+    ("wave_kernel", 12, 2, 16, 64, SIMPLE, False, TERMINAL, True, False),
+    # the straight paths_kernel: T = 16 and whole 2048-path chunks in a shape neither resident_kernel (P not a
+    # multiple of 4096) nor packed_kernel (P > 2048) takes: three chunks
+    ("paths_kernel+cf_kernel", 12, 16, 64, 96, LOG, True, ALL, True, False),
+    ("paths_kernel+cf_kernel", 12, 16, 64, 96, LOG, True, TERMINAL, True, False),
+    ("paths_kernel+cf_kernel", 12, 16, 64, 96, SIMPLE, True, ALL, True, False),
+    ("paths_kernel+cf_kernel", 12, 16, 64, 96, SIMPLE, True, TERMINAL, True, False),
+    # the other paths_kernel (one instantiation for either store mode) at an odd P: one padding element before the
+    # 8-byte-aligned terminal sum
+    ("paths_kernel+cf_kernel", 12, 7, 99, 7, LOG, True, ALL, True, False),
+    ("paths_kernel+cf_kernel", 12, 7, 99, 7, SIMPLE, True, ALL, True, False),
+    ("paths_kernel+cf_kernel", 12, 7, 99, 7, SIMPLE, True, TERMINAL, True, False),
+    # rows_kernel<float>
+    ("rows_kernel+cf_kernel", 12, 3, 64, 96, LOG, True, TERMINAL, True, False),
+    ("rows_kernel+cf_kernel", 12, 3, 64, 96, SIMPLE, True, ALL, True, False),
+    ("rows_kernel+cf_kernel", 12, 3, 64, 96, SIMPLE, True, TERMINAL, True, False),
+    ("rows_kernel+cf_kernel", 12, 17, 2048, 2, SIMPLE, True, TERMINAL, True, False),
+    # queue_kernel<float> in simple Euler, without and with row sums
+    ("queue_kernel", 12, 4, 99, 101, SIMPLE, True, ALL, False, True),
 ]
 
 
-@pytest.mark.parametrize("kernel,B,T,N,M,scheme,normalize,padded,sliced", TRAIN_CASES)
-def test_train_targets_paths_sums_and_targets(kernel, B, T, N, M, scheme, normalize, padded, sliced) -> None:
+def _case_id(case: tuple) -> str:
+    """The columns but the store mode, which only the terminal-row cases name."""
+    return "-".join(str(v) for v in case[:7] + case[8:]) + ("-terminal" if case[7] == TERMINAL else "")
+
+
+@pytest.mark.parametrize("kernel,B,T,N,M,scheme,normalize,store,padded,sliced", TRAIN_CASES,
+                         ids=[_case_id(c) for c in TRAIN_CASES])
+def test_train_targets_paths_sums_and_targets(kernel, B, T, N, M, scheme, normalize, store, padded, sliced) -> None:
     L = _lib.lib()
     P = N * M
     pitch = int(L.smc_path_pitch(P, 0)) if padded else P
@@ -123,14 +175,15 @@ def test_train_targets_paths_sums_and_targets(kernel, B, T, N, M, scheme, normal
     rows, _ = case_rows(scheme, normalize)
     for math, (_, flags) in MATHS.items():
         ref = _ref(B, T, P, scheme, normalize, math, N, M, keep_paths=True)
-        label = f"{kernel} T {T} N {N} M {M} {'log' if scheme == LOG else 'simple'} {'NORM' if normalize else 'RAW'} {math}"
-        got = _train_targets(rows[:B], T, N, M, scheme, normalize, flags, ALL, pitch, sliced=sliced)
-        used = _check_training(got, ref, ALL, label)
+        label = (f"{kernel} T {T} N {N} M {M} {'log' if scheme == LOG else 'simple'} {'NORM' if normalize else 'RAW'} "
+                 f"{'ALL' if store == ALL else 'TERMINAL'} {math}")
+        got = _train_targets(rows[:B], T, N, M, scheme, normalize, flags, store, pitch, sliced=sliced)
+        used = _check_training(got, ref, store, label)
         if math == "portable":
-            assert used["paths"] == _kernel_mode_paths_share(B, T, P, scheme, ref, ALL), label
+            assert used["paths"] == _kernel_mode_paths_share(B, T, P, scheme, ref, store), label
         if kernel in ("contract_kernel", "queue_kernel"):  # these also hand out every row's sum
-            got = _train_targets(rows[:B], T, N, M, scheme, normalize, flags, ALL, pitch, sliced=sliced, with_rowsum=True)
-            _check_training(got, ref, ALL, label + " with row sums")
+            got = _train_targets(rows[:B], T, N, M, scheme, normalize, flags, store, pitch, sliced=sliced, with_rowsum=True)
+            _check_training(got, ref, store, label + " with row sums")
 
 
 def test_sliced_resident_kernel_terminal_rows_and_targets() -> None:

@@ -43,7 +43,7 @@ def _rows(B: int, scheme: int, normalize: bool) -> tuple[np.ndarray, np.ndarray]
     return rows[pick], bars[pick]
 
 
-@functools.lru_cache(maxsize=2)
+@functools.lru_cache(maxsize=4)
 def _ref(typing: str, B: int, T: int, P: int, scheme: int, normalize: bool, N: int = 0, M: int = 0, bars: bool = False,
          keep_paths: bool = False) -> gref.GbmRef:
     """The reference of the first B case rows in the typing, once per shape, with its count condition."""
@@ -106,6 +106,14 @@ REF_CASES = [
     (12, 33, 64, 16, LOG, True, TERMINAL),    # T > 16, terminal rows
     (4, 4, 99, 101, SIMPLE, True, TERMINAL),  # P = 9999: a lane straddles P
     (600, 3, 64, 32, LOG, True, ALL),         # more contracts than the persistent grid
+    # the other cells of {log, simple} x {ALL, TERMINAL} at P = 700 and at P = 4096 (the eight instantiations
+    # rows_ref_kernel<LOG_EULER, STORE_ALL, HWN> are each reached above as well: tests/test_instantiation_ledger.py)
+    (12, 5, 100, 7, SIMPLE, True, TERMINAL),
+    (12, 5, 100, 7, LOG, True, ALL),
+    (12, 5, 100, 7, LOG, True, TERMINAL),
+    (12, 16, 64, 64, LOG, True, TERMINAL),
+    (12, 16, 64, 64, SIMPLE, True, ALL),
+    (12, 16, 64, 64, SIMPLE, True, TERMINAL),
 ]
 
 
@@ -140,6 +148,15 @@ F64_TRAIN_CASES = [
     ("rows_kernel+cf_kernel", 12, 5, 128, 32, SIMPLE, False, TERMINAL, True, False, False),
     ("rows_kernel+cf_kernel", 12, 2, 64, 64, LOG, True, ALL, True, False, False),    # the stream span
     ("queue_kernel", 3, 16, 128, 80, LOG, True, ALL, False, True, False),            # sliced: P = 10,240 > 8192
+    # ---- one row per instantiation (tests/test_instantiation_ledger.py) ----
+    # rows_kernel<double>: P = 2048, within one row block and beyond it
+    ("rows_kernel+cf_kernel", 12, 3, 64, 32, LOG, True, TERMINAL, True, False, False),
+    ("rows_kernel+cf_kernel", 12, 3, 64, 32, SIMPLE, True, ALL, True, False, False),
+    ("rows_kernel+cf_kernel", 12, 17, 64, 32, LOG, True, TERMINAL, True, False, False),
+    ("rows_kernel+cf_kernel", 12, 17, 64, 32, SIMPLE, True, ALL, True, False, False),
+    # queue_kernel<double> with row sums, and in simple Euler
+    ("queue_kernel", 3, 4, 128, 80, LOG, True, ALL, False, True, True),
+    ("queue_kernel", 3, 4, 128, 80, SIMPLE, True, ALL, False, True, True),
 ]
 
 
