@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general; smc_basket_greeks_general (with its _kernel and _cols queries) was added under 21 without a new number: the change is purely additive, no existing entry point moved, and the library ships together with the bindings that load it; smc_basket_price_paths (with its _kernel query) was added under 21 in the same way */
+#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general; smc_basket_greeks_general (with its _kernel and _cols queries) was added under 21 without a new number: the change is purely additive, no existing entry point moved, and the library ships together with the bindings that load it; smc_basket_price_paths (with its _kernel query) was added under 21 in the same way, and so was smc_gbm_greeks_paths (with its _kernel query) */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -815,6 +815,84 @@ int32_t smc_basket_price_paths(const double* contracts_dev /*[B][3A+4]*/,
  * rejects).  Static string, no device call. */
 const char* smc_basket_price_paths_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
                                           int32_t normalization);
+
+/* ---- batched Greeks of the Asian and lookback options (additive under ABI 21) -----
+ * Pathwise delta, vega, rho and theta of the Asian and fixed-strike lookback options smc_gbm_price_paths prices, with
+ * standard errors, for B contracts in ONE launch.  The pathwise method is exact for these payoffs (they are Lipschitz
+ * in the path); the knock-out payoffs are not (the knocked flag is discontinuous) and have no column here.  There is
+ * no gamma: the lognormal identity vega = v T X0^2 gamma of smc_gbm_greeks holds for a function of the terminal value
+ * only.  SMC_SCHEME_LOG_EULER only.
+ * Taken unchanged from smc_gbm_price_paths: the contract rows, the streams and the ordinal handling, the 512-lane
+ * workgroup per contract, 4 paths per lane, 2048-path chunks, validity for any n_paths >= 1, the monitoring dates
+ * (the T grid points; X0 is not monitored), K, df, the row sums, F_t and the scales s_t.
+ * Row t (0-based, steps = timesteps): x_t the raw value, xs_t = x_t s_t rounded to Real (s_t = 1 under RAW,
+ * F_t / Real(sumx_t / P) under NORMALIZE), tau_t the f64 grid point of F_t (tau = (t + 1) (T / steps), the last one T
+ * exactly), fr_t = (t + 1) / steps in f64, L_t = log(x_t / Real(X0)) (the portable f32 log; v_log_f32 times ln 2
+ * under SMC_MATH_HW; the library log in f64), mu = r - d - v^2 / 2.
+ * Per contract, each in f64 from the contract row, then rounded to Real: K, df (the price call's), ix0 = 1 / X0,
+ * cv = 1 / v (0 if v == 0), cT = 1 / (2 T) (0 if T == 0), rr = r, Tr = T.
+ * Per row, in f64, then rounded to Real (four tables in LDS: s_t and these three):
+ *   tr_t = tau_t                                                        (d ln xs_t / d r)
+ *   RAW:        av_t = -mu tau_t / v - v tau_t (0 if v == 0)            aT_t = mu / 2 * fr_t
+ *   NORMALIZE:  Lbar_t = sumxl_t / sumx_t
+ *               av_t = -Lbar_t / v (0 if v == 0)
+ *               aT_t = -Lbar_t / (2 T) + (r - d) fr_t    ((r - d) fr_t if T == 0)
+ * sumx_t is smc_gbm_price_paths' row sum bit for bit; sumxl_t = sum over the valid paths of f64(x_t * L_t) (the
+ * product in Real, each product cast and added singly), per lane over its chunks, then the wave butterfly, then
+ * waves 0..7.
+ * Per path and row, every operation rounded in Real (no fused multiply-add):
+ *   hv_t = L_t * cv + av_t          (d ln xs_t / d v)
+ *   hT_t = L_t * cT + aT_t          (d ln xs_t / d T, all monitoring dates moving in proportion with T)
+ *   sa += xs_t    sv += xs_t * hv_t    sT += xs_t * hT_t    sr += xs_t * tr_t
+ *   if (xs_t > mx) { mx = xs_t; Lmx = L_t; tmx = t }      (strict: the first row wins a tie)
+ *   if (xs_t < mn) { mn = xs_t; Lmn = L_t; tmn = t }
+ * At the end of a path the underlying u and its derivatives gv, gT, gr:
+ *   Asian          u = sa / steps    gv = sv / steps    gT = sT / steps    gr = sr / steps
+ *   lookback call  u = mx    gv = mx * (Lmx * cv + av[tmx])    gT = mx * (Lmx * cT + aT[tmx])    gr = mx * tr[tmx]
+ *   lookback put   the same with mn, Lmn, tmn
+ * and, with ip = K - u > 0 and ic = u - K > 0:
+ *   put = df * max(K - u, 0)        call = df * max(u - K, 0)
+ *   delta  put: ip ? -((df * u) * ix0) : 0            call: ic ? (df * u) * ix0 : 0
+ *   vega   put: ip ? -(df * gv) : 0                   call: ic ? df * gv : 0
+ *   rho    put: -(Tr * put) - (ip ? df * gr : 0)      call: -(Tr * call) + (ic ? df * gr : 0)
+ *   theta  put: rr * put + (ip ? df * gT : 0)         call: rr * call - (ic ? df * gT : 0)     (-d / d T, per year)
+ * each cast to f64 and added with its square (f64); a column's sum runs per lane over its chunks and paths in
+ * order, then the wave butterfly, then waves 0..7.  Under NORMALIZE these are the derivatives of the estimator
+ * smc_gbm_price_paths computes: the dependence of every row scale F_t / mean(x_t) on the parameter is included
+ * (that is Lbar_t); delta and rho need no correction, because x_t, F_t and the mean move alike.
+ * greeks_dev [B][40]; inside every group of four the order is Asian put, Asian call, lookback put, lookback call:
+ *    0..3  delta    4..7  vega    8..11  rho    12..15  theta
+ *   16..31 the standard errors of columns 0..15 (the price call's formula; 0 at P = 1)
+ *   32..35 the four prices: smc_gbm_price_paths' columns 0, 1, 4, 5 bit for bit (barriers_dev = NULL)
+ *   36..39 their standard errors: its columns 8, 9, 12, 13 bit for bit.
+ * The standard errors take the P terms as independent (they leave out the sampling error of the shared s_t and
+ * Lbar_t).  Conventions: v == 0 gives cv = av_t = 0; T == 0 drops the cT term; P == 1 gives every standard error 0.
+ * Passes.  RAW: the tables come from the contract row; one simulation (f32) takes all 40 sums.  NORMALIZE: pass 1
+ * takes sumx_t and sumxl_t as per-lane f64 accumulators in LDS ([2 R][512] doubles) in sweeps of R rows, each sweep
+ * simulating from row 0 to its last row; R is even, min(roundup2(T), what fits): the LDS a workgroup may take (144 KiB
+ * in f32; 160 KiB less the 51,232-byte table image of the path math in f64) less 2560 bytes of scratch and the four
+ * tables (4 roundup8(T sizeof(Real)) bytes), divided by 8192 and rounded down to even: 16 in f32 and 12 in f64 at
+ * T = 16.  A sweep boundary changes no sum's order.  Then the payoff simulation re-creates the same streams.  In f64
+ * the registers do not hold the 40 sums and the path state beside the step, so the Asian and the lookback columns are
+ * taken in two payoff simulations; a sum belongs to one of them and keeps its order, so no value depends on that.
+ * Checks, in smc_gbm_price_paths' order and all before the empty batch (n_contracts = 0: SMC_OK, nothing touched) is
+ * accepted.  SMC_ERR_INVALID_ARGUMENT: NULL contracts_dev, bad dtype, NULL greeks_dev, a scheme with unknown bits,
+ * SMC_MATH_REF, SMC_TRAIN_DYNAMIC or SMC_PRICE_REPLAY, SMC_MATH_HW with f64, bad normalization, then
+ * SMC_SCHEME_SIMPLE_EULER.  SMC_ERR_INVALID_SHAPE: n_contracts < 0 or >= 2^31, timesteps <= 0, n_paths <= 0 or
+ * >= 2^40; then, in both normalisations, timesteps whose four tables do not leave room for one sweep of two rows:
+ * 2560 + 4 roundup8(T sizeof(Real)) + 16384 bytes above the LDS named above (T > 8032 in f32, T > 2927 in f64).
+ * Stream-ordered: no allocation, no synchronisation, no workspace, no atomics, capturable into a graph.  B below the
+ * CU count leaves CUs idle.
+ * Out of scope: knock-out and knock-in Greeks (a pathwise estimator of them is biased); gamma and cross-Greeks;
+ * simple Euler; SMC_MATH_REF; basket path Greeks; continuous-monitoring corrections. */
+#define SMC_PATH_GREEKS_COLS 40
+int32_t smc_gbm_greeks_paths(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
+                             uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
+                             int32_t normalization, int32_t dtype, double* greeks_dev /*[B][40]*/, void* stream);
+/* "path_greeks_kernel(raw)", "path_greeks_kernel(replay)" or "unsupported" (a call smc_gbm_greeks_paths rejects).
+ * Static string, no device call. */
+const char* smc_gbm_greeks_paths_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                        int32_t dtype);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,13 @@ enum {
 };
 int32_t smc_test_math_eval(int32_t fn, const void* in_dev, int64_t n, void* out_dev, void* stream);
 
+/* The host plan of smc_gbm_greeks_paths for a shape (tests/test_path_greeks_host.py; no device call): *sweep_rows is R,
+ * the accumulator row pairs of a NORMALIZE sweep (0 under RAW), *lds_bytes the dynamic LDS of the launch.
+ * SMC_ERR_INVALID_ARGUMENT: hooks disabled, NULL pointer; SMC_ERR_INVALID_SHAPE: timesteps <= 0 or a shape, scheme or
+ * dtype path_greeks_kernel does not take. */
+int32_t smc_test_path_greeks_plan(int32_t timesteps, int32_t scheme, int32_t normalization, int32_t dtype,
+                                  int64_t* sweep_rows, int64_t* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

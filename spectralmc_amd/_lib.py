@@ -46,6 +46,7 @@ PATH_PRICE_COLS = 20  # doubles per contract smc_gbm_price_paths writes
 BASKET_PRICE_COLS = 18  # doubles per contract smc_basket_price writes
 BASKET_PATH_COLS = 25  # doubles per contract smc_basket_price_paths writes
 GREEKS_COLS = 26  # doubles per contract smc_gbm_greeks writes
+PATH_GREEKS_COLS = 40  # doubles per contract smc_gbm_greeks_paths writes
 ABI_VERSION = 21
 
 _c_i32, _c_i64, _c_u64, _c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
@@ -122,12 +123,17 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_basket_price_paths": (_c_i32, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i64,
                                         _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp, _c_vp, _c_vp]),
     "smc_basket_price_paths_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i32]),
+    "smc_gbm_greeks_paths": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32,
+                                      _c_vp, _c_vp]),
+    "smc_gbm_greeks_paths_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
 }
 
 # include/spectralmc_hip_testing.h: test-only entry points, inert unless SMC_ENABLE_TEST_HOOKS=1
 TEST_SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_test_exchange_fault": (_c_i32, [_c_i32, ctypes.c_uint32]),
     "smc_test_math_eval": (_c_i32, [_c_i32, _c_vp, _c_i64, _c_vp, _c_vp]),
+    "smc_test_path_greeks_plan": (_c_i32, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_i64),
+                                           ctypes.POINTER(_c_i64)]),
 }
 # smc_test_math_eval function ids (spectralmc_hip_testing.h SMC_TEST_MATH_*)
 TEST_MATH = {name: i for i, name in enumerate((

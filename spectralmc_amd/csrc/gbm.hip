@@ -23,6 +23,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -2278,6 +2279,316 @@ __global__ __launch_bounds__(kThreads) void greeks_kernel(EngineArgs a, double* 
   }
 }
 
+// ---- batched Greeks of the path-dependent payoffs: path_greeks_kernel (smc_gbm_greeks_paths) ----
+// path_price_kernel's geometry, streams, validity handling and sum order (restated, not shared: path_price_kernel's
+// registers stay as they are), log-Euler only.  Every monitored value is xs_t = x_t s_t, so its pathwise
+// derivatives follow from the row's log return L_t = log(x_t / X0) and per-row constants (the table of
+// include/spectralmc_hip.h): d ln xs_t / dv = L_t cv + av_t, d ln xs_t / dT = L_t cT + aT_t,
+// d ln xs_t / dr = tr_t, d ln xs_t / dX0 = 1 / X0.  The Asian payoff takes the running sums of xs_t times these,
+// the lookback payoffs the row of the extreme and its L.  Per path 20 terms in Real (delta, vega, rho, theta, price
+// of Asian put, Asian call, lookback put, lookback call), each cast to f64 and added with its square: kPathGreekSums
+// f64 sums per contract.
+//   RAW        one pass; the row tables come from the contract row alone.
+//   NORMALIZE  pass 1 takes two f64 sums per row, x and x L (the scale s_t = F_t / mean(x_t) moves with the
+//              parameters; its share is the x-weighted mean Lbar_t of L_t), as per-lane accumulators in dynamic LDS
+//              ([2 R][512] doubles, lane tid only ever touches column tid) in sweeps of R rows, each re-simulating
+//              from row 0 (R even); the thread that totals a row writes its four table entries.  Pass 2 re-creates
+//              the same streams.
+// ONE_PASS: all 20 terms in one payoff simulation (f32); otherwise the Asian and the lookback terms each get a
+// simulation of their own (f64: the 40 sums and the path state do not fit beside the f64 step).  A sum belongs
+// to one group and keeps its order, so no value depends on the grouping.
+constexpr int kPathGreekTerms = 20;
+constexpr int kPathGreekSums = 2 * kPathGreekTerms;
+constexpr size_t kPathGreekScratch = kWaves * kPathGreekSums * sizeof(double);
+constexpr int kPathGreekTables = 4;  // scales, tr, av, aT: T Reals each, padded to 8 B
+
+// tau_t of row_forward: times = linspace(dt, T, T) in f64, last point exact
+__device__ __forceinline__ double row_time(const Contract& c, int T, int t) {
+  const double dt = c.T / static_cast<double>(T);
+  const double step = T > 1 ? (c.T - dt) / static_cast<double>(T - 1) : 0.0;
+  return (t == T - 1) ? c.T : dt + static_cast<double>(t) * step;
+}
+
+// Row t's table entries from the f64 contract row (and, under NORMALIZE, the row's two sums), rounded to Real.
+template <typename Real, bool NORMALIZE>
+__device__ __forceinline__ void path_greeks_row(const Contract& c, int T, int t, int64_t P, double sumx, double sumxl,
+                                                Real* scales, Real* tr, Real* av, Real* aT) {
+  const double tau = row_time(c, T, t);
+  const double fr = static_cast<double>(t + 1) / static_cast<double>(T);
+  const double mu = c.r - c.d - 0.5 * c.v * c.v;
+  tr[t] = static_cast<Real>(tau);
+  if constexpr (NORMALIZE) {
+    const double lbar = sumxl / sumx;
+    scales[t] = row_forward<Real>(c, T, t) / static_cast<Real>(sumx / static_cast<double>(P));
+    av[t] = c.v == 0.0 ? Real(0) : static_cast<Real>(-lbar / c.v);
+    aT[t] = c.T == 0.0 ? static_cast<Real>((c.r - c.d) * fr)
+                       : static_cast<Real>(-lbar / (2.0 * c.T) + (c.r - c.d) * fr);
+  } else {
+    scales[t] = Real(1);
+    av[t] = c.v == 0.0 ? Real(0) : static_cast<Real>(-mu * tau / c.v - c.v * tau);
+    aT[t] = static_cast<Real>(mu / 2.0 * fr);
+  }
+}
+
+template <typename Real, bool HW, bool NORMALIZE>
+__global__ __launch_bounds__(kThreads) void path_greeks_kernel(EngineArgs a, double* __restrict__ greeks,
+                                                               int sweep_rows) {
+  // [kWaves][kPathGreekSums] scratch, then the four row tables, then (NORMALIZE) [2 sweep_rows][kThreads]
+  extern __shared__ double lds[];
+  if constexpr (sizeof(Real) == 8) math::f64_tables_load();
+  constexpr bool ONE_PASS = sizeof(Real) == 4;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const double* const row = hold_in_vgprs(a.contracts + b * 6);
+  double* const out = hold_in_vgprs(greeks + b * SMC_PATH_GREEKS_COLS);
+  const int nchunks = static_cast<int>((a.P + kChunk - 1) / kChunk);  // P < 2^40
+  const int64_t P = static_cast<int64_t>(hold_in_vgprs(static_cast<uint64_t>(a.P)));
+  const int64_t lane_left = P - kPathsPerLane * static_cast<int64_t>(tid);  // paths from the lane's first on
+  const Contract c = load_contract(row);
+  // f64: the stream keys wait in vector registers too (the f64 log's constants take the scalar ones)
+  uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+  uint64_t seed = a.seed;
+  if constexpr (sizeof(Real) == 8) {
+    ordinal = hold_in_vgprs(ordinal);
+    seed = hold_in_vgprs(seed);
+  }
+  const Stepper<Real, true, HW> step(c, T);
+  const Real x0 = static_cast<Real>(c.X0);
+  const size_t tab = (static_cast<size_t>(T) * sizeof(Real) + 7) / 8;  // doubles per table
+  Real* const scales = reinterpret_cast<Real*>(lds + kWaves * kPathGreekSums);
+  Real* const tr = reinterpret_cast<Real*>(lds + kWaves * kPathGreekSums + tab);
+  Real* const av = reinterpret_cast<Real*>(lds + kWaves * kPathGreekSums + 2 * tab);
+  Real* const aT = reinterpret_cast<Real*>(lds + kWaves * kPathGreekSums + 3 * tab);
+  double* const acc = lds + kWaves * kPathGreekSums + kPathGreekTables * tab;
+
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = lane_left - chunk;
+    return static_cast<int>(left <= 0 ? 0 : (left >= kPathsPerLane ? kPathsPerLane : left));
+  };
+
+  if constexpr (NORMALIZE) {
+    for (int t0 = 0; t0 < T; t0 += sweep_rows) {
+      const int nrows = T - t0 < sweep_rows ? T - t0 : sweep_rows;
+      for (int i = 0; i < 2 * nrows; ++i) acc[i * kThreads + tid] = 0.0;  // rows 2 i: x, 2 i + 1: x L
+      for (int ci = 0; ci < nchunks; ++ci) {
+        const int64_t chunk = static_cast<int64_t>(ci) * kChunk;
+        const int nvalid = valid_paths(chunk);
+        if (nvalid > 0) {
+          PathStream s(seed, ordinal, static_cast<uint64_t>((chunk + kPathsPerLane * tid) / kPathsPerLane), T);
+          double unused = 0.0;
+          Real xt[kPathsPerLane];
+          lane_rows_s<Real, true, HW, false, false>(
+              s, step, x0, chunk, nullptr, t0 + nrows, 0, unused, xt, tid, nullptr, 0,
+              [&](const Real(&x)[kPathsPerLane], int t) {
+                if (t >= t0) {  // t < t0 + nrows <= T: row t - t0 of this sweep, the lane's own column
+                  Real part = 0;
+#pragma unroll
+                  for (int j = 0; j < kPathsPerLane; ++j) part += j < nvalid ? x[j] : Real(0);
+                  double* const slot = acc + (2 * (t - t0)) * kThreads + tid;
+                  slot[0] += static_cast<double>(part);
+                  double sl = slot[kThreads];
+#pragma unroll
+                  for (int j = 0; j < kPathsPerLane; ++j)
+                    if (j < nvalid) sl += static_cast<double>(x[j] * greeks_log<Real, HW>(x[j], x0));
+                  slot[kThreads] = sl;
+                }
+              });
+        }
+      }
+      for (int i = 0; i < 2 * nrows; ++i) {
+        const double w = wave_sum(acc[i * kThreads + tid]);
+        if (lane == 0) acc[i * kThreads + tid] = w;  // the wave's sum, in its lane 0's own slot
+      }
+      __syncthreads();
+      if (tid < nrows) {
+        double totx = 0.0, totxl = 0.0;
+        for (int w = 0; w < kWaves; ++w) totx += acc[(2 * tid) * kThreads + w * 64];
+        for (int w = 0; w < kWaves; ++w) totxl += acc[(2 * tid + 1) * kThreads + w * 64];
+        // the contract row is read again where it is needed, so its six doubles are not held across the path loops
+        path_greeks_row<Real, true>(load_contract(row), T, t0 + tid, P, totx, totxl, scales, tr, av, aT);
+      }
+      __syncthreads();  // the accumulators are free for the next sweep
+    }
+  } else {
+    const Contract cr = load_contract(row);
+    for (int t = tid; t < T; t += kThreads) path_greeks_row<Real, false>(cr, T, t, P, 0.0, 0.0, scales, tr, av, aT);
+    __syncthreads();
+  }
+
+  // the contract's constants, each in f64 from the row, then rounded to Real (GreekConsts' conventions)
+  Real K, df, ix0, cv, cT, rr, Tr;
+  {
+    const Contract cr = load_contract(row);
+    const PayoffPre<Real> pre(cr);
+    K = pre.K;
+    df = pre.df;
+    ix0 = static_cast<Real>(1.0 / cr.X0);
+    cv = cr.v == 0.0 ? Real(0) : static_cast<Real>(1.0 / cr.v);
+    cT = cr.T == 0.0 ? Real(0) : static_cast<Real>(1.0 / (2.0 * cr.T));
+    rr = static_cast<Real>(cr.r);
+    Tr = static_cast<Real>(cr.T);
+  }
+  Real steps = static_cast<Real>(T);
+  if constexpr (sizeof(Real) == 8) {  // the f64 path math leaves no scalar registers for the uniform constants
+    auto keep = [](double& x) { x = __builtin_bit_cast(double, hold_in_vgprs(__builtin_bit_cast(uint64_t, x))); };
+    keep(K), keep(df), keep(ix0), keep(cv), keep(cT), keep(rr), keep(Tr), keep(steps);
+  }
+
+  // One payoff's five terms (delta, vega, rho, theta, price) from the underlying u and its derivatives, each cast
+  // to f64 and added with its square: v[i], v[5 + i].
+  auto add_terms = [&](bool is_put, Real u, Real gv, Real gT, Real gr, double* v) {
+    const Real diff = is_put ? K - u : u - K;
+    const bool in = diff > Real(0);
+    const Real pay = df * (in ? diff : Real(0));
+    const Real wd = (df * u) * ix0, wv = df * gv, wr = df * gr, wT = df * gT;
+    Real t[5];
+    if (is_put) {
+      t[0] = in ? -wd : Real(0);
+      t[1] = in ? -wv : Real(0);
+      t[2] = -(Tr * pay) - (in ? wr : Real(0));
+      t[3] = rr * pay + (in ? wT : Real(0));
+    } else {
+      t[0] = in ? wd : Real(0);
+      t[1] = in ? wv : Real(0);
+      t[2] = -(Tr * pay) + (in ? wr : Real(0));
+      t[3] = rr * pay - (in ? wT : Real(0));
+    }
+    t[4] = pay;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      const double d = static_cast<double>(t[i]);
+      v[i] += d;
+      v[5 + i] += d * d;
+    }
+  };
+
+  // A payoff simulation for the Asian payoffs, the lookback payoffs or both; its wave sums go to the scratch.
+  auto payoff_pass = [&](auto asian_tag, auto look_tag) {
+    constexpr bool ASIAN = decltype(asian_tag)::value, LOOK = decltype(look_tag)::value;
+    constexpr int NPAY = 2 * (ASIAN ? 1 : 0) + 2 * (LOOK ? 1 : 0);
+    double v[NPAY * 10];  // payoff q of the pass: terms v[10 q .. 10 q + 5), squares v[10 q + 5 .. 10 q + 10)
+#pragma unroll
+    for (int i = 0; i < NPAY * 10; ++i) v[i] = 0.0;
+    for (int ci = 0; ci < nchunks; ++ci) {
+      const int64_t chunk = static_cast<int64_t>(ci) * kChunk;
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        Real sa[kPathsPerLane], sv[kPathsPerLane], sT[kPathsPerLane], sr[kPathsPerLane];
+        Real mx[kPathsPerLane], mn[kPathsPerLane], Lmx[kPathsPerLane], Lmn[kPathsPerLane], xt[kPathsPerLane];
+        int tmx[kPathsPerLane], tmn[kPathsPerLane];
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j) {
+          sa[j] = sv[j] = sT[j] = sr[j] = Real(0);
+          mx[j] = -__builtin_huge_val();
+          mn[j] = __builtin_huge_val();
+          Lmx[j] = Lmn[j] = Real(0);
+          tmx[j] = tmn[j] = 0;
+        }
+        PathStream s(seed, ordinal, static_cast<uint64_t>((chunk + kPathsPerLane * tid) / kPathsPerLane), T);
+        double unused = 0.0;
+        lane_rows_s<Real, true, HW, false, false>(
+            s, step, x0, chunk, nullptr, T, 0, unused, xt, tid, nullptr, 0, [&](const Real(&x)[kPathsPerLane], int t) {
+              const Real sc = scales[t], trt = tr[t], avt = av[t], aTt = aT[t];  // t < T
+#pragma unroll
+              for (int j = 0; j < kPathsPerLane; ++j) {
+                // a lookback-only pass keeps the extreme row's x_t and takes its log after the rows: the same bits
+                const Real L = ASIAN ? greeks_log<Real, HW>(x[j], x0) : x[j];
+                const Real xs = NORMALIZE ? x[j] * sc : x[j];
+                if constexpr (ASIAN) {
+                  const Real hv = L * cv + avt;
+                  const Real hT = L * cT + aTt;
+                  sa[j] += xs;
+                  sv[j] += xs * hv;
+                  sT[j] += xs * hT;
+                  sr[j] += xs * trt;
+                }
+                if constexpr (LOOK) {
+                  if (xs > mx[j]) {
+                    mx[j] = xs;
+                    Lmx[j] = L;
+                    tmx[j] = t;
+                  }
+                  if (xs < mn[j]) {
+                    mn[j] = xs;
+                    Lmn[j] = L;
+                    tmn[j] = t;
+                  }
+                }
+              }
+            });
+#pragma unroll
+        for (int j = 0; j < kPathsPerLane; ++j) {
+          if (j < nvalid) {
+            if constexpr (ASIAN) {
+              const Real u = sa[j] / steps, gv = sv[j] / steps, gT = sT[j] / steps, gr = sr[j] / steps;
+              add_terms(true, u, gv, gT, gr, v);
+              add_terms(false, u, gv, gT, gr, v + 10);
+            }
+            if constexpr (LOOK) {
+              double* const vl = v + (ASIAN ? 20 : 0);
+              if constexpr (!ASIAN) {
+                Lmn[j] = greeks_log<Real, HW>(Lmn[j], x0);
+                Lmx[j] = greeks_log<Real, HW>(Lmx[j], x0);
+              }
+              {
+                const int t = tmn[j];  // < T: every valid path has T >= 1 rows
+                const Real u = mn[j];
+                add_terms(true, u, u * (Lmn[j] * cv + av[t]), u * (Lmn[j] * cT + aT[t]), u * tr[t], vl);
+              }
+              {
+                const int t = tmx[j];
+                const Real u = mx[j];
+                add_terms(false, u, u * (Lmx[j] * cv + av[t]), u * (Lmx[j] * cT + aT[t]), u * tr[t], vl + 10);
+              }
+            }
+          }
+        }
+      }
+    }
+    // wave butterfly; the wave's sums to the scratch at [wave][term], [wave][20 + term], term = 4 greek + payoff
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int q = 0; q < NPAY; ++q) {
+      const int payoff = q + (ASIAN ? 0 : 2);
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        const double w1 = wave_sum(v[10 * q + i]), w2 = wave_sum(v[10 * q + 5 + i]);
+        if (lane == 0) {
+          lds[wave * kPathGreekSums + 4 * i + payoff] = w1;
+          lds[wave * kPathGreekSums + kPathGreekTerms + 4 * i + payoff] = w2;
+        }
+      }
+    }
+  };
+  if constexpr (ONE_PASS) {
+    payoff_pass(std::true_type{}, std::true_type{});
+  } else {
+    payoff_pass(std::true_type{}, std::false_type{});
+    payoff_pass(std::false_type{}, std::true_type{});
+  }
+  __syncthreads();
+  if (tid < kPathGreekTerms) {  // term tid = 4 greek + payoff: its mean and standard error, waves 0..7
+    double s1 = 0.0, s2 = 0.0;
+    for (int w = 0; w < kWaves; ++w) s1 += lds[w * kPathGreekSums + tid];
+    for (int w = 0; w < kWaves; ++w) s2 += lds[w * kPathGreekSums + kPathGreekTerms + tid];
+    const double n = static_cast<double>(P);
+    const double m = s1 / n;
+    double se = 0.0;
+    if (P > 1) {
+      const double var = s2 - n * m * m;
+      se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+    }
+    if (tid < 16) {
+      out[tid] = m;
+      out[16 + tid] = se;
+    } else {  // the prices: columns 32..35 and 36..39
+      out[16 + tid] = m;
+      out[20 + tid] = se;
+    }
+  }
+}
+
 template <typename Real, bool HW>
 __global__ __launch_bounds__(256) void normals_kernel(uint64_t seed, uint64_t ordinal, int32_t rows,
                                                       int64_t cols, Real* __restrict__ out) {
@@ -2812,6 +3123,51 @@ int32_t launch_greeks(const EngineArgs& a, int mode, size_t lds, double* greeks,
   return launch_greeks_k<Real, false>(a, mode, lds, greeks, stream);
 }
 
+// path_greeks_kernel's plan for a shape (host only, no HIP call): 0 one RAW pass, 1 the NORMALIZE replay, -1 not a
+// scheme or flag set it takes, -2 more time steps than LDS holds row tables for.  *lds is the dynamic LDS: the
+// reduction scratch, the four row tables (scales, tr, av, aT; T Reals each, padded to 8 B) and, under NORMALIZE,
+// *rows accumulator row pairs (x and x L, [2 rows][512] doubles), rows even (T rounded up to even where that fits).
+// The bound on T is the same in both modes: the tables must leave room for one sweep of two rows.
+int path_greeks_plan(int32_t T, int32_t scheme, int32_t normalization, int32_t dtype, size_t* lds, int* rows) {
+  if (dtype != SMC_DTYPE_F32 && dtype != SMC_DTYPE_F64) return -1;
+  if ((scheme & 0xff) != SMC_SCHEME_LOG_EULER) return -1;
+  if ((scheme & SMC_MATH_REF) || ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)) return -1;
+  const size_t esz = dtype == SMC_DTYPE_F64 ? sizeof(double) : sizeof(float);
+  // the f64 kernels also hold the static table image of the path math
+  const size_t budget = dtype == SMC_DTYPE_F64 ? kMaxLds - sizeof(math::F64Tables) : kPathLdsBytes;
+  const size_t head = kPathGreekScratch + kPathGreekTables * ((static_cast<size_t>(T) * esz + 7) & ~size_t{7});
+  *lds = head;
+  *rows = 0;
+  if (head + 4 * kPathAccRow > budget) return -2;
+  if (normalization == SMC_NORM_RAW) return 0;
+  const size_t fit = ((budget - head) / (2 * kPathAccRow)) & ~size_t{1};
+  const size_t want = (static_cast<size_t>(T) + 1) & ~size_t{1};
+  *rows = static_cast<int>(want < fit ? want : fit);
+  *lds = head + static_cast<size_t>(*rows) * 2 * kPathAccRow;
+  return 1;
+}
+
+template <typename Real, bool HW>
+int32_t launch_path_greeks_k(const EngineArgs& a, size_t lds, int rows, double* greeks, hipStream_t stream) {
+  auto kernel = a.normalize ? path_greeks_kernel<Real, HW, true> : path_greeks_kernel<Real, HW, false>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SMC_ERR_HIP, "path_greeks_kernel: cannot raise the dynamic LDS limit");
+  }
+  launch(kernel, dim3(static_cast<unsigned>(a.B)), dim3(kThreads), static_cast<uint32_t>(lds), stream, a, greeks, rows);
+  return check_launch("path_greeks_kernel");
+}
+
+template <typename Real>
+int32_t launch_path_greeks(const EngineArgs& a, size_t lds, int rows, double* greeks, hipStream_t stream) {
+  if constexpr (sizeof(Real) == 4) {
+    if (a.scheme & SMC_MATH_HW) return launch_path_greeks_k<Real, true>(a, lds, rows, greeks, stream);
+  }
+  return launch_path_greeks_k<Real, false>(a, lds, rows, greeks, stream);
+}
+
 __global__ void advance_cursor_kernel(int64_t* cursor, int64_t advance) {
   if (threadIdx.x == 0) {
     cursor[0] += advance;
@@ -3291,6 +3647,71 @@ const char* smc_gbm_greeks_kernel(int32_t timesteps, int64_t n_paths, int32_t sc
     case kPriceReplay: return "greeks_kernel(replay)";
     default: return "unsupported";
   }
+}
+
+int32_t smc_gbm_greeks_paths(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
+                             uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
+                             int32_t normalization, int32_t dtype, double* greeks_dev, void* stream) {
+  if (int32_t st = validate_common(contracts_dev, n_contracts, timesteps, n_paths, dtype)) return st;
+  if (!greeks_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks_paths: greeks_dev is NULL");
+  if (!valid_scheme(scheme)) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks_paths: bad scheme");
+  if (scheme & SMC_MATH_REF)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_gbm_greeks_paths: SMC_MATH_REF is for smc_train_targets / smc_train_step");
+  if ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks_paths: SMC_MATH_HW is f32 only");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_greeks_paths: bad normalization");
+  if ((scheme & 0xff) != SMC_SCHEME_LOG_EULER)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_gbm_greeks_paths: SMC_SCHEME_SIMPLE_EULER is not supported (the reflected step is not a function "
+                "of the row's value); use SMC_SCHEME_LOG_EULER");
+  size_t lds = 0;
+  int rows = 0;
+  if (path_greeks_plan(timesteps, scheme, normalization, dtype, &lds, &rows) < 0)
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_gbm_greeks_paths: timesteps beyond the row tables a workgroup's LDS holds");
+  if (n_contracts == 0) return SMC_OK;
+  EngineArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.scheme = scheme;
+  a.normalize = normalization != SMC_NORM_RAW;
+  return dtype == SMC_DTYPE_F32 ? launch_path_greeks<float>(a, lds, rows, greeks_dev, as_stream(stream))
+                                : launch_path_greeks<double>(a, lds, rows, greeks_dev, as_stream(stream));
+}
+
+const char* smc_gbm_greeks_paths_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
+                                        int32_t dtype) {
+  size_t lds = 0;
+  int rows = 0;
+  if (timesteps <= 0 || n_paths <= 0 || n_paths >= (1LL << 40) || !valid_scheme(scheme) ||
+      (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE))
+    return "unsupported";
+  switch (path_greeks_plan(timesteps, scheme, normalization, dtype, &lds, &rows)) {
+    case 0: return "path_greeks_kernel(raw)";
+    case 1: return "path_greeks_kernel(replay)";
+    default: return "unsupported";
+  }
+}
+
+int32_t smc_test_path_greeks_plan(int32_t timesteps, int32_t scheme, int32_t normalization, int32_t dtype,
+                                  int64_t* sweep_rows, int64_t* lds_bytes) {
+  if (!test_hooks_enabled())
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_test_path_greeks_plan: test hooks disabled (SMC_ENABLE_TEST_HOOKS=1)");
+  if (!sweep_rows || !lds_bytes) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_test_path_greeks_plan: NULL pointer");
+  if (timesteps <= 0) return fail(SMC_ERR_INVALID_SHAPE, "smc_test_path_greeks_plan: timesteps <= 0");
+  size_t lds = 0;
+  int rows = 0;
+  if (path_greeks_plan(timesteps, scheme, normalization, dtype, &lds, &rows) < 0)
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_test_path_greeks_plan: not a shape path_greeks_kernel takes");
+  *sweep_rows = rows;
+  *lds_bytes = static_cast<int64_t>(lds);
+  return SMC_OK;
 }
 
 #pragma GCC visibility pop

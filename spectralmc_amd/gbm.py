@@ -305,6 +305,99 @@ class BlackScholes:
 
         model_config = ConfigDict(frozen=True, extra="forbid")
 
+    class PathBatchGreeks(BaseModel):
+        """``smc_gbm_greeks_paths``' block for B contracts, column by column: ``[B]`` f64 device tensors (pathwise
+        delta, vega, rho and theta = -dV/dT per year of the Asian and lookback options, their standard errors, and the
+        four prices ``price_paths_batch_device`` gives on the same paths with theirs)."""
+
+        model_config = ConfigDict(arbitrary_types_allowed=True, extra="forbid")
+        asian_put_delta: torch.Tensor
+        asian_call_delta: torch.Tensor
+        lookback_put_delta: torch.Tensor
+        lookback_call_delta: torch.Tensor
+        asian_put_vega: torch.Tensor
+        asian_call_vega: torch.Tensor
+        lookback_put_vega: torch.Tensor
+        lookback_call_vega: torch.Tensor
+        asian_put_rho: torch.Tensor
+        asian_call_rho: torch.Tensor
+        lookback_put_rho: torch.Tensor
+        lookback_call_rho: torch.Tensor
+        asian_put_theta: torch.Tensor
+        asian_call_theta: torch.Tensor
+        lookback_put_theta: torch.Tensor
+        lookback_call_theta: torch.Tensor
+        asian_put_delta_stderr: torch.Tensor
+        asian_call_delta_stderr: torch.Tensor
+        lookback_put_delta_stderr: torch.Tensor
+        lookback_call_delta_stderr: torch.Tensor
+        asian_put_vega_stderr: torch.Tensor
+        asian_call_vega_stderr: torch.Tensor
+        lookback_put_vega_stderr: torch.Tensor
+        lookback_call_vega_stderr: torch.Tensor
+        asian_put_rho_stderr: torch.Tensor
+        asian_call_rho_stderr: torch.Tensor
+        lookback_put_rho_stderr: torch.Tensor
+        lookback_call_rho_stderr: torch.Tensor
+        asian_put_theta_stderr: torch.Tensor
+        asian_call_theta_stderr: torch.Tensor
+        lookback_put_theta_stderr: torch.Tensor
+        lookback_call_theta_stderr: torch.Tensor
+        asian_put: torch.Tensor
+        asian_call: torch.Tensor
+        lookback_put: torch.Tensor
+        lookback_call: torch.Tensor
+        asian_put_stderr: torch.Tensor
+        asian_call_stderr: torch.Tensor
+        lookback_put_stderr: torch.Tensor
+        lookback_call_stderr: torch.Tensor
+
+    class HostPathGreeks(BaseModel):
+        """One contract's row of ``PathBatchGreeks`` on the host."""
+
+        asian_put_delta: float
+        asian_call_delta: float
+        lookback_put_delta: float
+        lookback_call_delta: float
+        asian_put_vega: float
+        asian_call_vega: float
+        lookback_put_vega: float
+        lookback_call_vega: float
+        asian_put_rho: float
+        asian_call_rho: float
+        lookback_put_rho: float
+        lookback_call_rho: float
+        asian_put_theta: float
+        asian_call_theta: float
+        lookback_put_theta: float
+        lookback_call_theta: float
+        asian_put_delta_stderr: float
+        asian_call_delta_stderr: float
+        lookback_put_delta_stderr: float
+        lookback_call_delta_stderr: float
+        asian_put_vega_stderr: float
+        asian_call_vega_stderr: float
+        lookback_put_vega_stderr: float
+        lookback_call_vega_stderr: float
+        asian_put_rho_stderr: float
+        asian_call_rho_stderr: float
+        lookback_put_rho_stderr: float
+        lookback_call_rho_stderr: float
+        asian_put_theta_stderr: float
+        asian_call_theta_stderr: float
+        lookback_put_theta_stderr: float
+        lookback_call_theta_stderr: float
+        asian_put: float
+        asian_call: float
+        lookback_put: float
+        lookback_call: float
+        asian_put_stderr: float
+        asian_call_stderr: float
+        lookback_put_stderr: float
+        lookback_call_stderr: float
+
+        model_config = ConfigDict(frozen=True, extra="forbid")
+
     #: path math of price_batch / price_batch_device and of price_paths_batch / price_paths_batch_device: "portable" (IEEE-only transcendentals, the draws and
     #: arithmetic of price / price_to_host) or "hw" (hardware f32 transcendentals, float32 engines only:
     #: throughput mode, within the f32 tolerance of "portable")
@@ -598,6 +691,65 @@ class BlackScholes:
             return res
         names = list(self.BatchGreeks.model_fields)
         return Success([self.HostGreeks(**dict(zip(names, row))) for row in res.value.cpu().tolist()])
+
+    # ------------------------------------------------------------------ batched Greeks of the path payoffs
+    def _greeks_paths_block(self, contracts: torch.Tensor) -> Result[torch.Tensor, NormalsError]:
+        """One ``smc_gbm_greeks_paths`` launch on the current stream (no sync): the ``[B, 40]`` f64 block of
+        contracts ``[B, 6]`` f64 on the device; contract b takes ordinal ``ordinal + b``."""
+        if self._cfg.path_scheme is not PathScheme.LOG_EULER:
+            raise ValueError(f"greeks_paths_batch needs PathScheme.LOG_EULER, got {self._cfg.path_scheme.name}: the "
+                             "pathwise Greeks are functions of the log-Euler row values")
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if contracts.ndim != 2 or contracts.shape[1] != len(FIELDS) or contracts.dtype != torch.float64:
+            raise ValueError(f"contracts must be a [B, {len(FIELDS)}] float64 tensor, got "
+                             f"{tuple(contracts.shape)} {contracts.dtype}")
+        _lib.require_device()
+        if not contracts.is_cuda:
+            raise ValueError("contracts must be a device tensor")
+        sp = self._sp
+        contracts = contracts.contiguous()
+        B = int(contracts.shape[0])
+        block = torch.empty((B, _lib.PATH_GREEKS_COLS), dtype=torch.float64, device=contracts.device)
+        if self.price_batch_math not in ("portable", "hw"):
+            raise ValueError(f"price_batch_math must be 'portable' or 'hw', got {self.price_batch_math!r}")
+        scheme = scheme_code(self._cfg.path_scheme) | (_lib.MATH_HW if self.price_batch_math == "hw" else 0)
+        if B:
+            _lib.check(_lib.lib().smc_gbm_greeks_paths(
+                _lib.ptr(contracts), B, sp.timesteps, sp.total_paths(), sp.mc_seed, None, self._served,
+                scheme, normalization_code(self._cfg.normalization), dtype_code(sp.dtype),
+                _lib.ptr(block), _lib.stream_handle()))
+            self._served += B
+        return Success(block)
+
+    def greeks_paths_batch_device(self, contracts: torch.Tensor
+                                  ) -> Result["BlackScholes.PathBatchGreeks", NormalsError]:
+        """Pathwise Greeks of the Asian and lookback put and call of B contracts (``[B, 6]`` f64 device tensor,
+        columns X0 K T r d v) in one launch of the fused kernel, with no path matrix in memory and no host sync:
+        the derivatives of the estimator ``price_paths_batch_device`` computes (without barriers), on the same
+        paths, with their standard errors.  LOG_EULER engines only.  Consumes the normal streams of B ``price``
+        calls."""
+        res = self._greeks_paths_block(contracts)
+        if isinstance(res, Failure):
+            return res
+        return Success(self.PathBatchGreeks(**dict(zip(self.PathBatchGreeks.model_fields, res.value.unbind(dim=1)))))
+
+    def greeks_paths_batch(self, inputs: "Sequence[BlackScholes.Inputs]"
+                           ) -> Result["list[BlackScholes.HostPathGreeks]", NormalsError]:
+        """``greeks_paths_batch_device`` from host values: one launch and one device-to-host copy."""
+        if self._cfg.path_scheme is not PathScheme.LOG_EULER:
+            raise ValueError(f"greeks_paths_batch needs PathScheme.LOG_EULER, got {self._cfg.path_scheme.name}: the "
+                             "pathwise Greeks are functions of the log-Euler row values")
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if len(inputs) == 0:
+            return Success([])
+        rows = [[float(getattr(c, f)) for f in FIELDS] for c in inputs]
+        res = self._greeks_paths_block(torch.tensor(rows, dtype=torch.float64, device=self._device()))
+        if isinstance(res, Failure):
+            return res
+        names = list(self.PathBatchGreeks.model_fields)
+        return Success([self.HostPathGreeks(**dict(zip(names, row))) for row in res.value.cpu().tolist()])
 
 
 def intrinsic_values(contract: "BlackScholes.Inputs") -> tuple[float, float, float]:
