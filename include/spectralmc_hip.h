@@ -800,8 +800,7 @@ int32_t smc_basket_greeks_general_cols(int32_t n_assets);
  * (n_contracts = 0: SMC_OK, nothing touched) is accepted.
  * Stream-ordered: no allocation, no synchronisation, no workspace, no atomics, capturable into a graph.  Nothing is
  * validated on the device (NaN barriers never knock; lower >= upper knocks every path).
- * Out of scope: Greeks of these payoffs; continuous-monitoring corrections; geometric averages; per-asset barrier
- * levels; a float64 basket engine; weights or a general correlation in the training targets. */
+ * Out of scope: continuous-monitoring corrections; geometric averages; per-asset barrier levels; a float64 basket engine; weights or a general correlation in the training targets. */
 #define SMC_BASKET_PATH_COLS 25
 int32_t smc_basket_price_paths(const double* contracts_dev /*[B][3A+4]*/,
                                const double* weights_dev /*rows of A, or NULL*/, int64_t weights_stride,
@@ -884,7 +883,7 @@ const char* smc_basket_price_paths_kernel(int32_t n_assets, int32_t timesteps, i
  * Stream-ordered: no allocation, no synchronisation, no workspace, no atomics, capturable into a graph.  B below the
  * CU count leaves CUs idle.
  * Out of scope: knock-out and knock-in Greeks (a pathwise estimator of them is biased); gamma and cross-Greeks;
- * simple Euler; SMC_MATH_REF; basket path Greeks; continuous-monitoring corrections. */
+ * simple Euler; SMC_MATH_REF; continuous-monitoring corrections. */
 #define SMC_PATH_GREEKS_COLS 40
 int32_t smc_gbm_greeks_paths(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
                              uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t scheme,
@@ -893,6 +892,93 @@ int32_t smc_gbm_greeks_paths(const double* contracts_dev, int64_t n_contracts, i
  * Static string, no device call. */
 const char* smc_gbm_greeks_paths_kernel(int32_t timesteps, int64_t n_paths, int32_t scheme, int32_t normalization,
                                         int32_t dtype);
+
+/* ---- Greeks of the Asian and lookback basket options (additive under ABI 21) -----
+ * Pathwise delta_i and vega_i per asset, rho and theta of the Asian and fixed-strike lookback options on the weighted
+ * basket level that smc_basket_price_paths prices, with standard errors, for B contracts in ONE launch:
+ * smc_gbm_greeks_paths' estimator, asset by asset.  An asset's volatility and spot move only that asset's rows
+ * (x_it = X0_i exp(mu_i tau_t + v_i W_it), and W does not depend on them).  The knock-out and worst-of payoffs have no
+ * column (a pathwise estimator of a knocked flag is biased); the European Greeks are smc_basket_greeks_general's.
+ * Taken unchanged from smc_basket_price_paths, the same in every respect: the contract rows ([B][3A+4]), the streams
+ * and the ordinal handling, weights_dev / weights_stride (NULL = f32(1.0 / A), stride 0 shares row 0, any sign),
+ * corr_dev / corr_stride (the packed strict lower triangle; NULL = the row's rho) and cholesky_general's factor, the
+ * step, one 512-lane workgroup per contract, 4 paths per lane, 2048-path chunks, validity for any n_paths >= 1, A in
+ * 1..8, K, df, the row sums, F_it, s_it, xs_it, and the f32 order of b_t and avg.
+ * Per contract, each in f64 from the contract row, then rounded to f32: K, df (the price call's), Tr = T, rr = r,
+ * cT = 1 / (2 T) (0 if T == 0), steps = f32(timesteps); per asset ix0_i = 1 / X0_i, cv_i = 1 / v_i (0 if v_i == 0),
+ * w_i, mu_i = r - d_i - v_i^2 / 2.
+ * Row t (0-based): tau_t = (t + 1) (T / timesteps) in f64, the last one T exactly; fr_t = (t + 1) / timesteps in f64.
+ * Per asset and row, in f64, then rounded to f32 (tables in LDS: s_it and av_it, aT_it per asset, tau_t per row):
+ *   RAW:        s_it = 1    av_it = -mu_i tau_t / v_i - v_i tau_t (0 if v_i == 0)    aT_it = mu_i / 2 * fr_t
+ *   NORMALIZE:  s_it = smc_basket_price_paths' scale bit for bit    Lbar_it = sumxl_it / sumx_it
+ *               av_it = -Lbar_it / v_i (0 if v_i == 0)
+ *               aT_it = -Lbar_it / (2 T) + (r - d_i) fr_t    ((r - d_i) fr_t if T == 0)
+ * sumx_it is smc_basket_price_paths' row sum bit for bit; sumxl_it = sum over the valid paths of f64(x_it * L_it) (the
+ * product in f32, each product cast and added singly), per lane over its chunks, then the wave butterfly, then waves
+ * 0..7.
+ * Per path and row, all in f32, every operation rounded (no fused multiply-add), assets i = 0 .. A - 1 in order:
+ *   L_it = log(x_it / f32(X0_i))  (the portable f32 log; v_log_f32 times ln 2 under SMC_MATH_HW)
+ *   xs_it = x_it * s_it (x_it under RAW)    wx_i = w_i * xs_it    b_t = ((0 + wx_0) + wx_1) + ...
+ *   hv_i = L_it * cv_i + av_it      hT_i = L_it * cT + aT_it      rowT = ((0 + wx_0 * hT_0) + wx_1 * hT_1) + ...
+ *   Asian:     sa += b_t    sd_i += wx_i    sv_i += wx_i * hv_i    sT += rowT    sr += b_t * tau_t
+ *   lookback:  if (b_t > mx) { mx = b_t; tmx = t; keep x_it for every i }   (strict: the first row wins a tie)
+ *              if (b_t < mn) { mn = b_t; tmn = t; keep x_it for every i }
+ * At the end of a path, the underlying u and its derivatives:
+ *   Asian     u = sa / steps    du_i = (sd_i / steps) * ix0_i    gv_i = sv_i / steps    gT = sT / steps
+ *             gr = sr / steps   wd_i = df * du_i    wv_i = df * gv_i
+ *   lookback  u = mx (call) or mn (put); with the kept x_i and the tables of row t* = tmx or tmn, wx_i, L_i, hv_i, hT_i
+ *             as above:  wd_i = (df * wx_i) * ix0_i    wv_i = df * (wx_i * hv_i)
+ *             gT = ((0 + wx_0 * hT_0) + wx_1 * hT_1) + ...    gr = u * tau_t*
+ * and, with ip = K - u > 0, ic = u - K > 0, put = df * max(K - u, 0), call = df * max(u - K, 0):
+ *   delta_i  put: ip ? -wd_i : 0                        call: ic ? wd_i : 0
+ *   vega_i   put: ip ? -wv_i : 0                        call: ic ? wv_i : 0
+ *   rho      put: -(Tr * put) - (ip ? df * gr : 0)      call: -(Tr * call) + (ic ? df * gr : 0)
+ *   theta    put: rr * put + (ip ? df * gT : 0)         call: rr * call - (ic ? df * gT : 0)    (-d / d T, per year,
+ *            all monitoring dates moving in proportion with T)
+ * each cast to f64 and added with its square (f64); a column's sum runs per lane over its chunks and paths in order,
+ * then the wave butterfly, then waves 0..7, sum k totalled by one thread.  A negative weight flips the signs by
+ * itself; nothing takes |w|.
+ * greeks_dev [B][16A+24].  Greek kinds g = 0 .. G - 1, G = 2A + 2: delta_0 .. delta_{A-1}, vega_0 .. vega_{A-1}, rho,
+ * theta.  Payoffs q = 0 .. 3: Asian put, Asian call, lookback put (K - min_t b_t), lookback call (max_t b_t - K).
+ *   4 g + q        Greek g of payoff q          4 G + 4 g + q   its standard error
+ *   8 G + q        the price of payoff q: smc_basket_price_paths' columns 0, 1, 4, 5 bit for bit (barriers_dev NULL)
+ *   8 G + 4 + q    its standard error: that call's columns 10, 11, 14, 15 bit for bit
+ * At A = 1 this is smc_gbm_greeks_paths' 40-column layout.  The standard errors take the P terms as independent.
+ * Conventions (smc_gbm_greeks_paths' and smc_basket_greeks_general's): v_i == 0 gives vega_i and its error 0; T == 0
+ * drops the cT term; P == 1 gives every standard error 0; nothing is validated on the device.
+ * Passes.  A payoff simulation takes at most 22 of the 8A + 12 terms.  A <= 4: two simulations, {Asian: every delta_i
+ * and vega_i, rho, theta, price} and {lookback put and call, all of theirs}.  A = 5..8: passes of at most 16 terms,
+ * {Asian: rho, theta, price}, then {Asian: delta_i, vega_i} over the assets in ranges of 4 (A = 5, 6: 0..3, 4..A-1) or
+ * of 2 (A = 7, 8: 0..1, 2..3, 4..5, 6..A-1), {lookback put: every delta_i, rho, theta, price}, {lookback put: every
+ * vega_i} and the same two for the lookback call: 7 simulations for A = 5, 6 and 9 for A = 7, 8.  A sum belongs to
+ * one pass and keeps its one order, so no value depends on the plan.  NORMALIZE first takes the 2 A timesteps row sums (sumx, sumxl) as per-lane
+ * f64 accumulators in LDS, in sweeps of whole dates (2A rows of 512 doubles per date), each sweep simulating from row
+ * 0 to its last row; the dates per sweep are what fits in 144 KiB beside 3328 bytes of scratch and the tables
+ * (roundup8(4 (3A + 1) timesteps) bytes).  There is no parked mode.
+ * math: 0 or SMC_MATH_HW.  SMC_PRICE_REPLAY is accepted and changes nothing; any other bit is rejected.
+ * Checks: smc_basket_price_paths' in its order and with its status codes, without the barrier argument (NULL
+ * contracts_dev, NULL greeks_dev, n_assets, math, normalization: SMC_ERR_INVALID_ARGUMENT; n_contracts, timesteps,
+ * n_paths: SMC_ERR_INVALID_SHAPE; weights_stride, corr_stride: SMC_ERR_INVALID_ARGUMENT); then, in both
+ * normalisations, SMC_ERR_INVALID_SHAPE for a shape whose tables leave no room for one date of accumulators
+ * (3328 + roundup8(4 (3A + 1) timesteps) + 8192 A bytes above 144 KiB); all before the empty batch (n_contracts = 0:
+ * SMC_OK, nothing touched) is accepted.
+ * Stream-ordered: no allocation, no synchronisation, no workspace, no atomics, no exchange between workgroups,
+ * capturable into a graph.
+ * Out of scope: correlation-pair sensitivities of these payoffs (the NORMALIZE correction would need A (A + 1) / 2
+ * moment sums per row); knock-out and worst-of Greeks; gammas; sensitivities to the weights; terminal_sum_dev; a
+ * float64 basket engine; continuous-monitoring corrections. */
+int32_t smc_basket_greeks_paths(const double* contracts_dev /*[B][3A+4]*/,
+                                const double* weights_dev /*rows of A, or NULL*/, int64_t weights_stride,
+                                const double* corr_dev /*rows of A(A-1)/2, or NULL*/, int64_t corr_stride,
+                                int64_t n_contracts, int32_t n_assets, int32_t timesteps, int64_t n_paths,
+                                uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0, int32_t math,
+                                int32_t normalization, double* greeks_dev /*[B][16A+24]*/, void* stream);
+/* "basket_path_greeks_kernel(raw)", "basket_path_greeks_kernel(replay)" or "unsupported" (a call
+ * smc_basket_greeks_paths rejects).  Static string, no device call. */
+const char* smc_basket_greeks_paths_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                           int32_t normalization);
+/* Doubles per contract of greeks_dev: 16 A + 24; -1 for n_assets outside 1..8. */
+int32_t smc_basket_greeks_paths_cols(int32_t n_assets);
 
 #ifdef __cplusplus
 }

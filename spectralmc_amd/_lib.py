@@ -126,6 +126,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_gbm_greeks_paths": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32,
                                       _c_vp, _c_vp]),
     "smc_gbm_greeks_paths_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
+    "smc_basket_greeks_paths": (_c_i32, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i64, _c_u64,
+                                         _c_vp, _c_i64, _c_i32, _c_i32, _c_vp, _c_vp]),
+    "smc_basket_greeks_paths_kernel": (ctypes.c_char_p, [_c_i32, _c_i32, _c_i64, _c_i32, _c_i32]),
+    "smc_basket_greeks_paths_cols": (_c_i32, [_c_i32]),
 }
 
 # include/spectralmc_hip_testing.h: test-only entry points, inert unless SMC_ENABLE_TEST_HOOKS=1
@@ -229,6 +233,15 @@ def basket_greeks_general_cols(n_assets: int) -> int:
     """Doubles per contract smc_basket_greeks_general writes for this asset count: 2 A^2 + 6 A + 12
     (smc_basket_greeks_general_cols)."""
     n = int(lib().smc_basket_greeks_general_cols(n_assets))
+    if n < 0:
+        raise ValueError(f"n_assets must be in 1..8, got {n_assets}")
+    return n
+
+
+def basket_path_greeks_cols(n_assets: int) -> int:
+    """Doubles per contract smc_basket_greeks_paths writes for this asset count: 16 A + 24
+    (smc_basket_greeks_paths_cols)."""
+    n = int(lib().smc_basket_greeks_paths_cols(n_assets))
     if n < 0:
         raise ValueError(f"n_assets must be in 1..8, got {n_assets}")
     return n

@@ -25,7 +25,8 @@ give the basket put's and call's per-asset deltas and vegas, rho, theta and corr
 (``smc_basket_greeks``; with ``weights=`` and / or ``correlation=`` those of the weighted, general-correlation basket, the
 correlation sensitivity per pair: ``smc_basket_greeks_general``).  ``basket_price_paths`` / ``BasketEngine.price_paths``
 price the path-dependent payoffs of that basket over the monitoring dates (Asian, knock-out, lookback, worst-of
-knock-out: ``smc_basket_price_paths``).
+knock-out: ``smc_basket_price_paths``); ``basket_greeks_paths`` / ``BasketEngine.greeks_paths`` give the per-asset
+deltas and vegas, rho and theta of the Asian and lookback ones (``smc_basket_greeks_paths``).
 """
 
 from __future__ import annotations
@@ -447,6 +448,108 @@ def basket_price_paths(contracts: torch.Tensor, cfg: BasketConfig, *, barriers: 
     return BasketPathPrices(**{name: block[:, col] for col, name in enumerate(BASKET_PATH_FIELDS)}, terminal_sum=tsum,
                             block=block)
 
+PATH_GREEK_PAYOFFS = ("asian_put", "asian_call", "lookback_put", "lookback_call")
+
+
+def basket_path_greeks_fields(n_assets: int) -> tuple[str, ...]:
+    """The names of ``smc_basket_greeks_paths``'s 16A + 24 columns in order.  Greek kinds ``delta_0`` ..
+    ``delta_{A-1}``, ``vega_0`` .. ``vega_{A-1}``, ``rho``, ``theta``, each for the four payoffs of
+    ``PATH_GREEK_PAYOFFS`` (``delta_asian_put_0``, ``delta_asian_call_0``, ``delta_lookback_put_0``, ...), the same
+    names with ``_stderr``, the four prices and their ``_stderr``."""
+    if not 1 <= n_assets <= MAX_ASSETS:
+        raise ValueError(f"n_assets must be in 1..{MAX_ASSETS}, got {n_assets}")
+    means = tuple(f"{kind}_{pay}_{i}" for kind in ("delta", "vega") for i in range(n_assets)
+                  for pay in PATH_GREEK_PAYOFFS)
+    means += tuple(f"{kind}_{pay}" for kind in ("rho", "theta") for pay in PATH_GREEK_PAYOFFS)
+    return means + tuple(m + "_stderr" for m in means) + PATH_GREEK_PAYOFFS + tuple(
+        p + "_stderr" for p in PATH_GREEK_PAYOFFS)
+
+
+@dataclass(frozen=True)
+class BasketPathGreeks:
+    """``smc_basket_greeks_paths``'s block for B contracts of A assets.  Every field is a view of ``block``
+    [B, 16A + 24] (``basket_path_greeks_fields`` order): per payoff of ``PATH_GREEK_PAYOFFS`` the per-asset ``delta_*``
+    and ``vega_*`` [B, A], ``rho_*`` and ``theta_*`` (-dV/dT per year, every monitoring date moving with T) [B], their
+    ``_stderr``, and the four prices with theirs (``smc_basket_price_paths``'s columns 0, 1, 4, 5 and 10, 11, 14, 15
+    bit for bit)."""
+    delta_asian_put: torch.Tensor
+    delta_asian_call: torch.Tensor
+    delta_lookback_put: torch.Tensor
+    delta_lookback_call: torch.Tensor
+    vega_asian_put: torch.Tensor
+    vega_asian_call: torch.Tensor
+    vega_lookback_put: torch.Tensor
+    vega_lookback_call: torch.Tensor
+    rho_asian_put: torch.Tensor
+    rho_asian_call: torch.Tensor
+    rho_lookback_put: torch.Tensor
+    rho_lookback_call: torch.Tensor
+    theta_asian_put: torch.Tensor
+    theta_asian_call: torch.Tensor
+    theta_lookback_put: torch.Tensor
+    theta_lookback_call: torch.Tensor
+    delta_asian_put_stderr: torch.Tensor
+    delta_asian_call_stderr: torch.Tensor
+    delta_lookback_put_stderr: torch.Tensor
+    delta_lookback_call_stderr: torch.Tensor
+    vega_asian_put_stderr: torch.Tensor
+    vega_asian_call_stderr: torch.Tensor
+    vega_lookback_put_stderr: torch.Tensor
+    vega_lookback_call_stderr: torch.Tensor
+    rho_asian_put_stderr: torch.Tensor
+    rho_asian_call_stderr: torch.Tensor
+    rho_lookback_put_stderr: torch.Tensor
+    rho_lookback_call_stderr: torch.Tensor
+    theta_asian_put_stderr: torch.Tensor
+    theta_asian_call_stderr: torch.Tensor
+    theta_lookback_put_stderr: torch.Tensor
+    theta_lookback_call_stderr: torch.Tensor
+    asian_put: torch.Tensor
+    asian_call: torch.Tensor
+    lookback_put: torch.Tensor
+    lookback_call: torch.Tensor
+    asian_put_stderr: torch.Tensor
+    asian_call_stderr: torch.Tensor
+    lookback_put_stderr: torch.Tensor
+    lookback_call_stderr: torch.Tensor
+    block: torch.Tensor
+
+
+def _path_greeks_views(block: torch.Tensor, A: int) -> dict[str, torch.Tensor]:
+    """The named views of a [B, 16A + 24] block (the column table of include/spectralmc_hip.h): Greek g of payoff q
+    is column 4 g + q."""
+    G = 2 * A + 2
+    out: dict[str, torch.Tensor] = {}
+    for suffix, base in (("", 0), ("_stderr", 4 * G)):
+        for q, pay in enumerate(PATH_GREEK_PAYOFFS):
+            out[f"delta_{pay}{suffix}"] = block[:, base + q:base + 4 * A:4]
+            out[f"vega_{pay}{suffix}"] = block[:, base + 4 * A + q:base + 8 * A:4]
+            out[f"rho_{pay}{suffix}"] = block[:, base + 8 * A + q]
+            out[f"theta_{pay}{suffix}"] = block[:, base + 8 * A + 4 + q]
+    for q, pay in enumerate(PATH_GREEK_PAYOFFS):
+        out[pay] = block[:, 8 * G + q]
+        out[pay + "_stderr"] = block[:, 8 * G + 4 + q]
+    return out
+
+
+def basket_greeks_paths(contracts: torch.Tensor, cfg: BasketConfig, *, weights: torch.Tensor | None = None,
+                        correlation: torch.Tensor | None = None, ordinal0: int = 0, n_paths: int | None = None,
+                        validate: bool = False) -> BasketPathGreeks:
+    """Pathwise Greeks of the Asian and lookback basket options ``basket_price_paths`` prices, for device contracts
+    [B, 3A+4] f64: per-asset deltas and vegas, rho and theta with standard errors and the four prices, in one launch
+    of ``smc_basket_greeks_paths`` on the current stream, no host synchronisation.  ``cfg``, ``n_paths``, ``weights``
+    and ``correlation`` as ``basket_price_paths``'s (there are no barriers: the knock-out payoffs have no pathwise
+    Greeks).  ``validate=True`` checks the values first (``validate_basket_inputs``) and is the only path that
+    synchronises."""
+    c = _batched_call(contracts, cfg, n_paths, weights, correlation, validate)
+    B, A = c.B, c.A
+    block = torch.empty((B, _lib.basket_path_greeks_cols(A)), dtype=torch.float64, device=contracts.device)
+    if B > 0:
+        _lib.check(_lib.lib().smc_basket_greeks_paths(
+            _lib.ptr(contracts), _lib.ptr(c.weights), c.w_stride, _lib.ptr(c.tri), c.c_stride, B, A, cfg.timesteps,
+            c.P, cfg.mc_seed, None, ordinal0, c.math, c.norm, _lib.ptr(block), _lib.stream_handle()))
+    return BasketPathGreeks(**_path_greeks_views(block, A), block=block)
+
 
 def basket_greeks_fields(n_assets: int) -> tuple[str, ...]:
     """The names of ``smc_basket_greeks``'s 8A + 16 columns in order: per-asset ``delta_put_i``, ``delta_call_i``,
@@ -745,6 +848,16 @@ class BasketEngine:
                                   barriers=barriers, weights=weights, correlation=correlation, ordinal0=ordinal0,
                                   n_paths=n_paths, validate=validate)
 
+    def greeks_paths(self, contracts: torch.Tensor | None = None, *, weights: torch.Tensor | None = None,
+                     correlation: torch.Tensor | None = None, ordinal0: int = 0, n_paths: int | None = None,
+                     validate: bool = False) -> BasketPathGreeks:
+        """Pathwise Greeks of the Asian and lookback basket options (``basket_greeks_paths``) with the engine's
+        configuration, by default of the contracts of the last enqueued step.  The other arguments as
+        ``basket_greeks_paths``'s."""
+        return basket_greeks_paths(self.buffers.contracts if contracts is None else contracts, self.cfg,
+                                   weights=weights, correlation=correlation, ordinal0=ordinal0, n_paths=n_paths,
+                                   validate=validate)
+
 
 def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) -> None:
     """Make ``pricer`` train on basket contracts: its training sessions build a ``BasketEngine``
@@ -756,7 +869,8 @@ def use_basket_engine(pricer, cfg: BasketConfig, *, store_paths: bool = True) ->
     pricer.mc_engine_factory = factory
 
 
-__all__ = ["BASKET_PATH_FIELDS", "BasketConfig", "BasketEngine", "BasketGeneralGreeks", "BasketGreeks", "BasketPathPrices",
-           "BasketPrices", "basket_fields", "basket_general_greeks_fields", "basket_greeks", "basket_greeks_fields",
-           "basket_price", "basket_price_paths", "basket_targets", "default_basket_bounds", "pack_correlation",
+__all__ = ["BASKET_PATH_FIELDS", "PATH_GREEK_PAYOFFS", "BasketConfig", "BasketEngine", "BasketGeneralGreeks",
+           "BasketGreeks", "BasketPathGreeks", "BasketPathPrices", "BasketPrices", "basket_fields",
+           "basket_general_greeks_fields", "basket_greeks", "basket_greeks_fields", "basket_greeks_paths",
+           "basket_path_greeks_fields", "basket_price", "basket_price_paths", "basket_targets", "default_basket_bounds", "pack_correlation",
            "unpack_correlation", "use_basket_engine", "validate_basket_barriers", "validate_basket_inputs", "MAX_ASSETS"]

@@ -1899,6 +1899,383 @@ __global__ __launch_bounds__(kBThreads) void basket_greeks_general_kernel(Basket
   }
 }
 
+// ---- Greeks of the Asian and lookback basket options: basket_path_greeks_kernel (smc_basket_greeks_paths) ----
+// basket_path_kernel's front end, row hook and sweeps of whole dates (restated, not shared: its registers stay as
+// they are) with path_greeks_kernel's per-row log-derivative tables, asset by asset: asset i's volatility and spot
+// move only its own rows, so with L_it = log(x_it / X0_i) the row tables av_it, aT_it, tau_t and s_it give
+// d ln xs_it / dv_i = L_it cv_i + av_it, / dT = L_it cT + aT_it, / dr = tau_t, / dX0_i = 1 / X0_i (the table of
+// include/spectralmc_hip.h).  8A + 12 per-path f32 terms, each cast to f64 and added with its square.
+//   tables     [T][3A + 1] f32 in LDS in both normalisations: s_it, av_it, aT_it per asset, then tau_t.
+//   NORMALIZE  first the 2 A T row sums (x and x L per asset and row) as per-lane f64 accumulators in dynamic LDS
+//              ([dates * 2A][512], lane tid touches column tid only) in sweeps of whole dates, each re-simulating
+//              from row 0; the thread that totals an (asset, row) pair writes its three table entries.
+// Passes (basket_pg_pass): a payoff simulation takes at most 22 terms.  A <= 4: {Asian, all assets, rho, theta,
+// price}, {lookback put and call, all of theirs}.  A = 5..8, passes of at most 16 terms: Asian {rho, theta, price},
+// then the assets in ranges of 4 (A = 5, 6: {0..3}, {4..A-1}) or of 2 (A = 7, 8: {0, 1}, {2, 3}, {4, 5}, {6..A-1});
+// lookback put {deltas, rho, theta, price}, {vegas}; lookback call likewise: 7 passes for A = 5, 6 and 9 for A = 7, 8.
+// A lookback pass keeps the A raw values of the extreme row and takes their logs after the rows.  A sum belongs to
+// one pass and keeps its order, so no value depends on the plan.
+struct BasketPGPass {
+  bool asian, lmin, lmax;
+  bool scal;  // Asian: rho, theta and the price ride along; lookback: the deltas, rho, theta and the price are taken
+  bool vega;  // lookback: the vegas are taken
+  int a0, a1;  // Asian: the assets whose delta and vega the pass takes
+};
+constexpr int basket_pg_range(int A) { return A <= 6 ? 4 : 2; }  // assets per Asian delta / vega pass (A >= 5)
+constexpr int basket_pg_ranges(int A) { return (A + basket_pg_range(A) - 1) / basket_pg_range(A); }
+constexpr int basket_pg_passes(int A) { return A <= 4 ? 2 : 5 + basket_pg_ranges(A); }
+constexpr BasketPGPass basket_pg_pass(int A, int p) {
+  if (A <= 4)
+    return p == 0 ? BasketPGPass{true, false, false, true, false, 0, A}
+                  : BasketPGPass{false, true, true, true, true, 0, A};
+  const int nr = basket_pg_ranges(A), rs = basket_pg_range(A);
+  if (p == 0) return BasketPGPass{true, false, false, true, false, 0, 0};
+  if (p <= nr) return BasketPGPass{true, false, false, false, false, (p - 1) * rs, p * rs < A ? p * rs : A};
+  return p == nr + 1   ? BasketPGPass{false, true, false, true, false, 0, A}
+         : p == nr + 2 ? BasketPGPass{false, true, false, false, true, 0, A}
+         : p == nr + 3 ? BasketPGPass{false, false, true, true, false, 0, A}
+                       : BasketPGPass{false, false, true, false, true, 0, A};
+}
+constexpr int basket_pg_extreme_terms(BasketPGPass p, int A) { return (p.scal ? A + 3 : 0) + (p.vega ? A : 0); }
+constexpr int basket_pg_terms(BasketPGPass p, int A) {
+  return p.asian ? 4 * (p.a1 - p.a0) + (p.scal ? 6 : 0)
+                 : ((p.lmin ? 1 : 0) + (p.lmax ? 1 : 0)) * basket_pg_extreme_terms(p, A);
+}
+constexpr int kBPGMaxTerms = 22;
+// scratch at the head of the dynamic LDS: pass partials [kBWaves][2 kBPGMaxTerms] and the Cholesky factor [8][8]
+// (f64; 3328 B)
+constexpr int kBPGHead = kBWaves * 2 * kBPGMaxTerms + kMaxAssets * kMaxAssets;
+constexpr size_t kBPGScratch = kBPGHead * sizeof(double);
+static_assert(kBPGScratch == 3328 && kBPGScratch % 16 == 0, "the header states the scratch bytes");
+
+template <int A, bool HW, bool NORMALIZE>
+__global__ __launch_bounds__(kBThreads) void basket_path_greeks_kernel(BasketArgs a, BasketGeneralArgs g,
+                                                                       double* __restrict__ greeks, int sweep_dates) {
+  constexpr int NP = basket_pg_passes(A);
+  constexpr int REC = 3 * A + 1;   // a row's table record: s [A], av [A], aT [A], tau
+  constexpr int NG = 2 * A + 2;    // Greek kinds
+  constexpr int RED = 2 * kBPGMaxTerms;
+  // kBPGHead doubles of scratch; the tables ([T][REC] f32, padded to 8 B); NORMALIZE: the accumulator rows
+  // ([sweep_dates * 2A][512])
+  extern __shared__ double lds[];
+  double* Ld = lds + kBWaves * RED;  // [8][8]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const int T = a.T;
+  const int64_t P = a.P;
+  float* tab = reinterpret_cast<float*>(lds + kBPGHead);
+  double* acc = lds + kBPGHead + (static_cast<size_t>(REC) * T * sizeof(float) + 7) / 8;
+
+  const double* c = a.contracts + b * (3 * A + 4);
+  const double Tm = c[1], r = c[2], rho = c[3];
+  if (tid == 0) cholesky_general(A, rho, g.corr ? g.corr + b * g.corr_stride : nullptr, Ld);
+  __syncthreads();
+  // per-asset log2-unit coefficients, as basket_kernel
+  const double dt = Tm / static_cast<double>(T);
+  const double sq = sqrt(dt);
+  constexpr double zscale = HW ? PathStream::kNormalScale<true> : 1.0;
+  float ca[A], x0[A], Lb[A][A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double v = c[4 + 2 * A + i], d = c[4 + A + i];
+    const double drift = r - d - 0.5 * v * v;
+    ca[i] = static_cast<float>(drift * dt * kBLog2e);
+    const double bi = v * sq * kBLog2e * zscale;
+    x0[i] = static_cast<float>(c[4 + i]);
+#pragma unroll
+    for (int k = 0; k < A; ++k) Lb[i][k] = k <= i ? static_cast<float>(bi * Ld[i * kMaxAssets + k]) : 0.0f;
+  }
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+
+  auto uniform = [](float f) {  // the same for every lane: kept in a scalar register
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, f)));
+  };
+  auto valid_paths = [&](int64_t chunk) {  // how many of the lane's 4 values of this chunk are paths (< P)
+    const int64_t left = P - chunk - kBPaths * static_cast<int64_t>(tid);
+    return static_cast<int>(left <= 0 ? 0 : (left >= kBPaths ? kBPaths : left));
+  };
+  // Row t's table entries of asset i from the f64 contract row (and, under NORMALIZE, the pair's two sums)
+  auto write_entry = [&](int t, int i, double sumx, double sumxl) {
+    const double v = c[4 + 2 * A + i], rd = r - c[4 + A + i];
+    const double mu = rd - 0.5 * v * v;
+    const double tau = t == T - 1 ? Tm : static_cast<double>(t + 1) * dt;
+    const double fr = static_cast<double>(t + 1) / static_cast<double>(T);
+    float* rec = tab + static_cast<size_t>(t) * REC;
+    if (i == 0) rec[3 * A] = static_cast<float>(tau);
+    if constexpr (NORMALIZE) {
+      const float F = static_cast<float>(c[4 + i]) * math::exp_any(static_cast<float>(rd) * static_cast<float>(tau));
+      const double lbar = sumxl / sumx;
+      rec[i] = F / static_cast<float>(sumx / static_cast<double>(P));
+      rec[A + i] = v == 0.0 ? 0.0f : static_cast<float>(-lbar / v);
+      rec[2 * A + i] = Tm == 0.0 ? static_cast<float>(rd * fr) : static_cast<float>(-lbar / (2.0 * Tm) + rd * fr);
+    } else {
+      rec[i] = 1.0f;
+      rec[A + i] = v == 0.0 ? 0.0f : static_cast<float>(-mu * tau / v - v * tau);
+      rec[2 * A + i] = static_cast<float>(mu / 2.0 * fr);
+    }
+  };
+
+  if constexpr (NORMALIZE) {
+    for (int t0 = 0; t0 < T; t0 += sweep_dates) {
+      const int nd = T - t0 < sweep_dates ? T - t0 : sweep_dates;
+      const int nrows = 2 * nd * A;  // <= the rows the host sized acc for; row 2 (d A + i): x, the next one: x L
+      for (int q = 0; q < nrows; ++q) acc[q * kBThreads + tid] = 0.0;
+      for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+        const int nvalid = valid_paths(chunk);
+        if (nvalid > 0) {
+          PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+          float x[A][kBPaths];
+          basket_lane_paths<A, HW>(s, ca, x0, Lb, t0 + nd, x, [&](const float(&xr)[A][kBPaths], int t) {
+            if (t >= t0) {  // t < t0 + nd: date t - t0 of this sweep, the lane's own column
+              double* row = acc + static_cast<size_t>(t - t0) * 2 * A * kBThreads + tid;
+#pragma unroll
+              for (int i = 0; i < A; ++i) {
+                float p = 0.0f;  // basket_path_kernel's row sum: the valid values left to right in f32 from 0
+#pragma unroll
+                for (int j = 0; j < kBPaths; ++j) p += j < nvalid ? xr[i][j] : 0.0f;
+                row[(2 * i) * kBThreads] += static_cast<double>(p);
+                double sl = row[(2 * i + 1) * kBThreads];
+#pragma unroll
+                for (int j = 0; j < kBPaths; ++j)
+                  if (j < nvalid) sl += static_cast<double>(xr[i][j] * basket_greeks_log<HW>(xr[i][j], x0[i]));
+                row[(2 * i + 1) * kBThreads] = sl;
+              }
+            }
+          });
+        }
+      }
+      for (int q = 0; q < nrows; ++q) {  // wave butterfly into lane 0's own slot
+        const double w = bwave_sum(acc[q * kBThreads + tid]);
+        if (lane == 0) acc[q * kBThreads + tid] = w;
+      }
+      __syncthreads();
+      if (tid < nd * A) {  // pair tid = d A + i: waves 0..7 of its two sums, then its table entries
+        double sumx = 0.0, sumxl = 0.0;
+        for (int w = 0; w < kBWaves; ++w) sumx += acc[(2 * tid) * kBThreads + w * 64];
+        for (int w = 0; w < kBWaves; ++w) sumxl += acc[(2 * tid + 1) * kBThreads + w * 64];
+        const int d = tid / A;
+        write_entry(t0 + d, tid - d * A, sumx, sumxl);
+      }
+      __syncthreads();  // the accumulators are free for the next sweep
+    }
+  } else {
+    for (int idx = tid; idx < A * T; idx += kBThreads) {
+      const int t = idx / A;
+      write_entry(t, idx - t * A, 0.0, 0.0);
+    }
+    __syncthreads();
+  }
+
+  // payoff constants (basket_path_kernel's), the weights and the per-asset constants of the table
+  const float Tf = static_cast<float>(Tm);
+  const float df = math::exp_any(static_cast<float>(-r) * Tf);
+  const float Kf = static_cast<float>(c[0]);
+  const float steps = static_cast<float>(T);
+  const float cT = Tm == 0.0 ? 0.0f : static_cast<float>(1.0 / (2.0 * Tm));
+  const float rr = static_cast<float>(r);
+  float wt[A], ix0[A], cv[A];
+#pragma unroll
+  for (int i = 0; i < A; ++i) {
+    const double v = c[4 + 2 * A + i];
+    wt[i] = uniform(g.weights ? static_cast<float>(g.weights[b * g.weights_stride + i]) : static_cast<float>(1.0 / A));
+    ix0[i] = uniform(static_cast<float>(1.0 / c[4 + i]));
+    cv[i] = uniform(v == 0.0 ? 0.0f : static_cast<float>(1.0 / v));
+  }
+  const float inf = __builtin_huge_valf();
+  const double n = static_cast<double>(P);
+  double* out = greeks + b * (8 * NG + 8);
+
+  basket_static_for(std::make_integer_sequence<int, NP>{}, [&](auto tag) {
+    constexpr BasketPGPass PS = basket_pg_pass(A, decltype(tag)::value);
+    constexpr int NTP = basket_pg_terms(PS, A);
+    constexpr bool ASIAN = PS.asian, LMIN = PS.lmin, LMAX = PS.lmax, SCAL = PS.scal, VEGA = PS.vega;
+    constexpr int A0 = PS.a0, A1 = PS.a1, NR = A1 - A0 > 0 ? A1 - A0 : 1;
+    constexpr int NE = basket_pg_extreme_terms(PS, A);  // a lookback payoff's terms in this pass
+    constexpr int V0 = SCAL ? A : 0;                    // the first vega among them (after the deltas)
+    constexpr int S0 = VEGA ? 2 * A : A;                // rho, theta, price (after the deltas and the vegas)
+    static_assert(NTP <= kBPGMaxTerms, "pass partials");
+    double v[2 * NTP];  // term k of the pass: v[k], its squares: v[NTP + k]
+#pragma unroll
+    for (int k = 0; k < 2 * NTP; ++k) v[k] = 0.0;
+    auto add = [&](int k, float t) {
+      const double d = static_cast<double>(t);
+      v[k] += d;
+      v[NTP + k] += d * d;
+    };
+    // a lookback payoff's terms (delta_i, then vega_i, then rho, theta, price: those the pass takes) from its extreme
+    // u, the extreme's row te and the A raw values there
+    auto extreme_terms = [&](bool is_put, float u, int te, const float(&xe)[A][kBPaths], int j, int base) {
+      const float* rec = tab + static_cast<size_t>(te) * REC;  // te < T: every valid path has T >= 1 rows
+      const float diff = is_put ? Kf - u : u - Kf;
+      const bool in = diff > 0.0f;
+      const float pay = df * (in ? diff : 0.0f);
+      float gT = 0.0f;
+#pragma unroll
+      for (int i = 0; i < A; ++i) {
+        const float xs = NORMALIZE ? xe[i][j] * rec[i] : xe[i][j];
+        const float wx = wt[i] * xs;
+        const float L = basket_greeks_log<HW>(xe[i][j], x0[i]);
+        const float wd = (df * wx) * ix0[i];
+        const float wv = df * (wx * (L * cv[i] + rec[A + i]));
+        gT = gT + wx * (L * cT + rec[2 * A + i]);
+        if constexpr (SCAL) add(base + i, in ? (is_put ? -wd : wd) : 0.0f);
+        if constexpr (VEGA) add(base + V0 + i, in ? (is_put ? -wv : wv) : 0.0f);
+      }
+      if constexpr (SCAL) {
+        const float wr = df * (u * rec[3 * A]), wT = df * gT;
+        add(base + S0, is_put ? -(Tf * pay) - (in ? wr : 0.0f) : -(Tf * pay) + (in ? wr : 0.0f));
+        add(base + S0 + 1, is_put ? rr * pay + (in ? wT : 0.0f) : rr * pay - (in ? wT : 0.0f));
+        add(base + S0 + 2, pay);
+      }
+    };
+    for (int64_t chunk = 0; chunk < P; chunk += kBChunk) {
+      const int nvalid = valid_paths(chunk);
+      if (nvalid > 0) {
+        float sa[kBPaths], sT[kBPaths], sr[kBPaths], sd[NR][kBPaths], sv[NR][kBPaths];
+        float mn[kBPaths], mx[kBPaths], xmn[A][kBPaths], xmx[A][kBPaths];
+        int tmn[kBPaths], tmx[kBPaths];
+#pragma unroll
+        for (int j = 0; j < kBPaths; ++j) {
+          sa[j] = sT[j] = sr[j] = 0.0f;
+          mn[j] = inf;
+          mx[j] = -inf;
+          tmn[j] = tmx[j] = 0;
+#pragma unroll
+          for (int i = 0; i < A1 - A0; ++i) sd[i][j] = sv[i][j] = 0.0f;
+#pragma unroll
+          for (int i = 0; i < A; ++i) xmn[i][j] = xmx[i][j] = x0[i];
+        }
+        PathStream s(a.seed, ordinal, static_cast<uint64_t>(chunk / kBPaths + tid));
+        float x[A][kBPaths];
+        basket_lane_paths<A, HW>(s, ca, x0, Lb, T, x, [&](const float(&xr)[A][kBPaths], int t) {
+          const float* rec = tab + static_cast<size_t>(t) * REC;
+#pragma unroll
+          for (int j = 0; j < kBPaths; ++j) {
+            float wx[A];
+            float bt = 0.0f;
+#pragma unroll
+            for (int i = 0; i < A; ++i) {
+              const float xs = NORMALIZE ? xr[i][j] * rec[i] : xr[i][j];
+              wx[i] = wt[i] * xs;
+              bt = bt + wx[i];
+            }
+            if constexpr (ASIAN) {
+              sa[j] = sa[j] + bt;
+              float L[A];
+#pragma unroll
+              for (int i = 0; i < A; ++i)
+                if (SCAL || (i >= A0 && i < A1)) L[i] = basket_greeks_log<HW>(xr[i][j], x0[i]);
+#pragma unroll
+              for (int i = A0; i < A1; ++i) {
+                sd[i - A0][j] = sd[i - A0][j] + wx[i];
+                sv[i - A0][j] = sv[i - A0][j] + wx[i] * (L[i] * cv[i] + rec[A + i]);
+              }
+              if constexpr (SCAL) {
+                float rowT = 0.0f;
+#pragma unroll
+                for (int i = 0; i < A; ++i) rowT = rowT + wx[i] * (L[i] * cT + rec[2 * A + i]);
+                sT[j] = sT[j] + rowT;
+                sr[j] = sr[j] + bt * rec[3 * A];
+              }
+            }
+            if constexpr (LMIN) {
+              if (bt < mn[j]) {  // strict: the first row wins a tie
+                mn[j] = bt;
+                tmn[j] = t;
+#pragma unroll
+                for (int i = 0; i < A; ++i) xmn[i][j] = xr[i][j];
+              }
+            }
+            if constexpr (LMAX) {
+              if (bt > mx[j]) {
+                mx[j] = bt;
+                tmx[j] = t;
+#pragma unroll
+                for (int i = 0; i < A; ++i) xmx[i][j] = xr[i][j];
+              }
+            }
+          }
+        });
+#pragma unroll
+        for (int j = 0; j < kBPaths; ++j) {
+          if (j < nvalid) {
+            if constexpr (ASIAN) {
+              const float avg = sa[j] / steps;
+              const float dp = Kf - avg, dc = avg - Kf;
+              const bool ip = dp > 0.0f, ic = dc > 0.0f;
+              const float put = df * (ip ? dp : 0.0f), call = df * (ic ? dc : 0.0f);
+#pragma unroll
+              for (int i = 0; i < A1 - A0; ++i) {
+                const float wd = df * ((sd[i][j] / steps) * ix0[A0 + i]);
+                const float wv = df * (sv[i][j] / steps);
+                add(4 * i, ip ? -wd : 0.0f);
+                add(4 * i + 1, ic ? wd : 0.0f);
+                add(4 * i + 2, ip ? -wv : 0.0f);
+                add(4 * i + 3, ic ? wv : 0.0f);
+              }
+              if constexpr (SCAL) {
+                const float wr = df * (sr[j] / steps), wT = df * (sT[j] / steps);
+                add(4 * (A1 - A0), -(Tf * put) - (ip ? wr : 0.0f));
+                add(4 * (A1 - A0) + 1, -(Tf * call) + (ic ? wr : 0.0f));
+                add(4 * (A1 - A0) + 2, rr * put + (ip ? wT : 0.0f));
+                add(4 * (A1 - A0) + 3, rr * call - (ic ? wT : 0.0f));
+                add(4 * (A1 - A0) + 4, put);
+                add(4 * (A1 - A0) + 5, call);
+              }
+            }
+            if constexpr (LMIN) extreme_terms(true, mn[j], tmn[j], xmn, j, 0);
+            if constexpr (LMAX) extreme_terms(false, mx[j], tmx[j], xmx, j, LMIN ? NE : 0);
+          }
+        }
+      }
+    }
+    // the pass's sums: wave butterfly, waves 0..7, sum k totalled by thread k alone
+#pragma unroll
+    for (int k = 0; k < 2 * NTP; ++k) {
+      const double w = bwave_sum(v[k]);
+      if (lane == 0) lds[wave * RED + k] = w;
+    }
+    __syncthreads();
+    if (tid < NTP) {  // a term's mean and standard error, and its column: Greek kind gk of payoff q, or price q
+      auto total = [&](int k) {
+        double t2 = 0.0;
+        for (int w = 0; w < kBWaves; ++w) t2 += lds[w * RED + k];
+        return t2;
+      };
+      const double m = total(tid) / n;
+      double se = 0.0;
+      if (P > 1) {
+        const double var = total(NTP + tid) - n * m * m;
+        se = sqrt((var > 0.0 ? var : 0.0) / (n - 1.0) / n);
+      }
+      int gk, q;
+      if constexpr (ASIAN) {
+        if (tid < 4 * (A1 - A0)) {
+          const int i = A0 + (tid >> 2), sub = tid & 3;
+          gk = sub < 2 ? i : A + i;
+          q = sub & 1;
+        } else {
+          const int kk = tid - 4 * (A1 - A0);  // rho put, rho call, theta put, theta call, put, call
+          gk = 2 * A + (kk >> 1);
+          q = kk & 1;
+        }
+      } else {
+        const int e = tid / NE, kk = tid - e * NE;  // delta_i, vega_i, rho, theta, price: those the pass takes
+        gk = SCAL ? (VEGA || kk < A ? kk : A + kk) : A + kk;
+        q = LMIN ? 2 + e : 3;
+      }
+      if (gk < NG) {
+        out[4 * gk + q] = m;
+        out[4 * NG + 4 * gk + q] = se;
+      } else {
+        out[8 * NG + q] = m;
+        out[8 * NG + 4 + q] = se;
+      }
+    }
+    if (NP > 1) __syncthreads();  // the partials are rewritten by the next pass
+  });
+}
+
 
 // ---- basket_resident_kernel: the terminal rows never leave the chip ------------------------------
 // A C5 contract's terminal rows are A x P f32 = 2 MiB, far beyond one CU, so W = P / 4096
@@ -2550,6 +2927,25 @@ int basket_path_plan(int A, int32_t T, int64_t P, int32_t math, int32_t normaliz
   return 1;
 }
 
+// basket_path_greeks_kernel's plan for a shape (host only, no HIP call): 0 the RAW passes, 1 the NORMALIZE replay,
+// -1 not a call it takes, -2 row tables (3 A + 1 f32 per date) that leave no room for one date of accumulators (2 A
+// rows), in either normalisation.  *dates is the number of whole time rows per sweep (NORMALIZE), *lds the dynamic LDS.
+int basket_path_greeks_plan(int A, int32_t T, int64_t P, int32_t math, int32_t normalization, size_t* lds, int* dates) {
+  if (T <= 0 || !basket_plan_ok(A, P, math, normalization)) return -1;
+  *dates = 0;
+  const size_t date = 2 * static_cast<size_t>(A) * kBPathAccRow;
+  const size_t tables = static_cast<size_t>(3 * A + 1) * static_cast<size_t>(T) * sizeof(float);
+  if (tables > kBPathLdsBytes) return -2;
+  const size_t head = kBPGScratch + ((tables + 7) & ~size_t{7});
+  *lds = head;
+  if (head + date > kBPathLdsBytes) return -2;
+  if (normalization == SMC_NORM_RAW) return 0;
+  const size_t fit = (kBPathLdsBytes - head) / date;  // >= 1
+  *dates = static_cast<int>(static_cast<size_t>(T) < fit ? static_cast<size_t>(T) : fit);
+  *lds = head + static_cast<size_t>(*dates) * date;
+  return 1;
+}
+
 }  // namespace
 }  // namespace smc
 
@@ -2757,6 +3153,48 @@ const char* smc_basket_price_paths_kernel(int32_t n_assets, int32_t timesteps, i
     case 1: return "basket_path_kernel(replay)";
     default: return "unsupported";
   }
+}
+
+int32_t smc_basket_greeks_paths(const double* contracts_dev, const double* weights_dev, int64_t weights_stride,
+                                const double* corr_dev, int64_t corr_stride, int64_t n_contracts, int32_t n_assets,
+                                int32_t timesteps, int64_t n_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                                int64_t ordinal0, int32_t math, int32_t normalization, double* greeks_dev,
+                                void* stream) {
+  const BasketCall c{"smc_basket_greeks_paths", contracts_dev, n_contracts, n_assets, timesteps, n_paths,
+                     mc_seed, ordinal_dev, ordinal0, math, normalization};
+  if (int32_t st = check_basket_call(c, "greeks_dev", greeks_dev)) return st;
+  if (int32_t st = check_basket_strides(c, weights_dev, weights_stride, corr_dev, corr_stride)) return st;
+  size_t lds = 0;
+  int dates = 0;
+  if (basket_path_greeks_plan(n_assets, timesteps, n_paths, math, normalization, &lds, &dates) < 0)
+    return fail(SMC_ERR_INVALID_SHAPE,
+                "smc_basket_greeks_paths: the row tables of n_assets * timesteps leave no room for one date of "
+                "accumulators in LDS");
+  if (n_contracts == 0) return SMC_OK;
+  const BasketArgs a = basket_args(c, nullptr);
+  const BasketGeneralArgs g = basket_general_args(c, weights_dev, weights_stride, corr_dev, corr_stride);
+  const auto pick = [](auto A, auto HW, auto NORM) { return basket_path_greeks_kernel<A(), HW(), NORM()>; };
+  return with_variant(n_assets, math & SMC_MATH_HW, c.entry, [&](auto A, auto HW) {
+    return with_flag(a.normalize, [&](auto NORM) {
+      return launch_per_contract(pick(A, HW, NORM), "basket_path_greeks_kernel", c.B, lds, as_stream(stream), a, g,
+                                 greeks_dev, dates);
+    });
+  });
+}
+
+const char* smc_basket_greeks_paths_kernel(int32_t n_assets, int32_t timesteps, int64_t n_paths, int32_t math,
+                                           int32_t normalization) {
+  size_t lds = 0;
+  int dates = 0;
+  switch (basket_path_greeks_plan(n_assets, timesteps, n_paths, math, normalization, &lds, &dates)) {
+    case 0: return "basket_path_greeks_kernel(raw)";
+    case 1: return "basket_path_greeks_kernel(replay)";
+    default: return "unsupported";
+  }
+}
+
+int32_t smc_basket_greeks_paths_cols(int32_t n_assets) {
+  return n_assets < 1 || n_assets > kMaxAssets ? -1 : 16 * n_assets + 24;
 }
 
 #pragma GCC visibility pop
