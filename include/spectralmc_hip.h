@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general; smc_basket_greeks_general (with its _kernel and _cols queries) was added under 21 without a new number: the change is purely additive, no existing entry point moved, and the library ships together with the bindings that load it; smc_basket_price_paths (with its _kernel query) was added under 21 in the same way, and so was smc_gbm_greeks_paths (with its _kernel query) */
+#define SMC_ABI_VERSION 21  /* 16: smc_gbm_price; 17: smc_gbm_price_paths; 18: smc_basket_price; 19: smc_gbm_greeks; 20: smc_basket_greeks; 21: smc_basket_price_general; smc_basket_greeks_general (with its _kernel and _cols queries) was added under 21 without a new number: the change is purely additive, no existing entry point moved, and the library ships together with the bindings that load it; smc_basket_price_paths (with its _kernel query) was added under 21 in the same way, so was smc_gbm_price_sliced (with its _workspace_bytes and _kernel queries and smc_gbm_price_slice_paths), and so was smc_gbm_greeks_paths (with its _kernel query) */
 
 /* ---- status codes ------------------------------------------------------- */
 #define SMC_OK                      0
@@ -979,6 +979,59 @@ const char* smc_basket_greeks_paths_kernel(int32_t n_assets, int32_t timesteps, 
                                            int32_t normalization);
 /* Doubles per contract of greeks_dev: 16 A + 24; -1 for n_assets outside 1..8. */
 int32_t smc_basket_greeks_paths_cols(int32_t n_assets);
+
+/* ---- sliced batched pricing: one contract across workgroups (additive under ABI 21) -----
+ * smc_gbm_price's 8 columns with each contract cut into W = ceil(n_paths / slice_paths) slices of slice_paths paths
+ * (a positive multiple of 2048, the 512 x 4 chunk; the last slice is ragged and ends at n_paths), one 512-lane
+ * workgroup per (contract, slice), B W workgroups in all: for one contract, or a few dozen, at a path count where
+ * one workgroup per contract leaves most of the chip idle.
+ * Taken unchanged from smc_gbm_price: the contract rows, the streams (contract b uses ordinal (*ordinal_dev or 0) +
+ * ordinal0 + b; the lane group of paths p0..p0+3 the stream (seed, ordinal, p0 / 4, timesteps) with the contract-
+ * global p0), the step, the payoff arithmetic in the sim dtype, SMC_MATH_HW (f32 only), the columns.
+ * Order.  Inside a slice, smc_gbm_price's order over the slice's own chunks: per lane over the chunks with paths
+ * ascending (the lane's 4 raw terminal values summed in the sim dtype first), the wave butterfly xor 32..1, waves
+ * 0..7; lanes wholly past the slice end neither draw nor contribute.  A workgroup leaves six f64 partials in the
+ * workspace: the raw terminal sum, put, call, underlying, put^2, call^2.  The six totals of a contract are slice 0's
+ * value, then + slice 1, ..., + slice W - 1; the 8 columns are smc_gbm_price's closing arithmetic on the totals (the
+ * standard errors, 0 at n_paths = 1; the intrinsic values; column 7 the total raw sum).  Under SMC_NORM_NORMALIZE
+ * the scale is F / Real(total / n_paths) from the total raw sum.  So the block is bit-identical run to run, under any
+ * split of the batch, and for slice_paths >= n_paths (W = 1) it is smc_gbm_price | SMC_PRICE_REPLAY's bit for bit; for
+ * W > 1 the f64 sums are associated differently (by slice), the last bits of columns 0..4 and 7 may differ from
+ * smc_gbm_price's, and in portable f32 math column 7 is the oracle's kernel-mode row sum at span = slice_paths.
+ * Launches, in stream order on `stream`: SMC_NORM_RAW two (price_slice_kernel with the payoffs at scale 1, then
+ * price_finish_kernel); SMC_NORM_NORMALIZE four (price_slice_kernel for the sums; price_finish_kernel for the totals;
+ * price_slice_kernel again, replaying its slice's streams with the payoffs at the scale from the total;
+ * price_finish_kernel for the columns).  No atomics, no arrival counters, no waiting on memory, no assumption that
+ * workgroups are co-resident; capturable into a graph; no allocation, no synchronisation.
+ * workspace_dev: smc_gbm_price_sliced_workspace_bytes bytes = 8 n_contracts (6 W + 1), 8-byte aligned: partials
+ * [B][W][6], then totals [B].  It needs no zeroing (every slot read was written earlier in the same call) and holds
+ * nothing between calls.
+ * Checks, in this order, all before the empty batch (n_contracts = 0: SMC_OK, nothing touched) is accepted:
+ * smc_gbm_price's (NULL contracts_dev: SMC_ERR_INVALID_ARGUMENT; n_contracts < 0 or >= 2^31, timesteps <= 0,
+ * n_paths <= 0 or >= 2^40: SMC_ERR_INVALID_SHAPE; dtype, NULL prices_dev, bad scheme or unknown flag, SMC_MATH_REF,
+ * SMC_MATH_HW with f64, bad normalization: SMC_ERR_INVALID_ARGUMENT); SMC_PRICE_REPLAY or SMC_TRAIN_DYNAMIC:
+ * SMC_ERR_INVALID_ARGUMENT (there is no mode to force); slice_paths <= 0 or not a multiple of 2048:
+ * SMC_ERR_INVALID_SHAPE; W > 65,535 or n_contracts W >= 2^31: SMC_ERR_INVALID_SHAPE; NULL workspace_dev or
+ * workspace_bytes below the query: SMC_ERR_INVALID_ARGUMENT.
+ * Out of scope: sliced Greeks and sliced path-dependent or basket pricing (the same pattern with more partials; the
+ * workspace layout [B][W][k] and the slice rule are meant to carry over); parking slices to save the NORMALIZE
+ * replay; a slice length chosen from the batch size. */
+int32_t smc_gbm_price_sliced(const double* contracts_dev /*[B][6]*/, int64_t n_contracts, int32_t timesteps,
+                             int64_t n_paths, int64_t slice_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                             int64_t ordinal0, int32_t scheme, int32_t normalization, int32_t dtype,
+                             double* prices_dev /*[B][8]*/, void* workspace_dev, int64_t workspace_bytes,
+                             void* stream);
+/* 8 n_contracts (6 W + 1); -1 for arguments the call rejects (n_contracts < 0 or >= 2^31, n_paths <= 0 or >= 2^40,
+ * slice_paths <= 0 or not a multiple of 2048, W > 65,535, n_contracts W >= 2^31). */
+int64_t     smc_gbm_price_sliced_workspace_bytes(int64_t n_contracts, int64_t n_paths, int64_t slice_paths);
+/* The default slice length, from n_paths alone: 2048 max(1, ceil(n_paths / (2048 x 512))), 512 being two workgroups
+ * on each of 256 CUs; so the block a default call gives does not change with the batch size or the device.  -1 for
+ * n_paths <= 0 or >= 2^40. */
+int64_t     smc_gbm_price_slice_paths(int64_t n_paths);
+/* "price_slice_kernel(raw)", "price_slice_kernel(replay)" or "unsupported" (a shape, scheme, normalization or dtype
+ * the call rejects).  Static string, no device call. */
+const char* smc_gbm_price_sliced_kernel(int32_t timesteps, int64_t n_paths, int64_t slice_paths, int32_t scheme,
+                                        int32_t normalization, int32_t dtype);
 
 #ifdef __cplusplus
 }

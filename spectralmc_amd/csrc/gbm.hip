@@ -1851,6 +1851,145 @@ __global__ __launch_bounds__(kThreads) void price_kernel(EngineArgs a, double* _
   }
 }
 
+// ---- sliced batched pricing: price_slice_kernel + price_finish_kernel (smc_gbm_price_sliced) ----
+// A contract cut into W = ceil(P / slice_paths) slices (slice_paths a multiple of kChunk, the last slice ends at
+// P), one workgroup per (contract, slice): workgroup blockIdx.x = b W + w.  Inside its slice a workgroup is
+// price_kernel over the slice's chunks (restated, not shared: price_kernel's registers stay as they are): the
+// streams PathStream(seed, ordinal, p0 / 4, T) with the contract-global p0, the lane's 4 raw terminal values
+// summed in Real first, per lane over the slice's chunks in ascending order, wave butterfly xor 32..1, waves
+// 0..7; lanes wholly past the slice end neither draw nor contribute.  Nothing survives a launch but the workspace,
+// so there is no parked mode: NORMALIZE replays the slice's streams once the contract's total is known.
+//   kSliceRaw  RAW: the raw sum and the five payoff sums at scale 1, one pass;
+//   kSliceSum  NORMALIZE pass 1: the raw sum only;
+//   kSlicePay  NORMALIZE pass 2: the payoff sums at the scale from the contract's total raw sum (ws totals).
+// Workspace (doubles): partials [B][W][kSliceSums] (raw sum, put, call, underlying, put^2, call^2), then totals
+// [B].  Every slot read was written earlier in the same call (stream order): no zeroing, no atomics, no counters.
+// price_finish_kernel adds a contract's W partials in slice order (slice 0's value, + slice 1, ...), one thread
+// per (contract, sum), and closes with price_kernel's arithmetic.
+enum PriceSlicePass : int { kSliceRaw = 0, kSliceSum = 1, kSlicePay = 2 };
+constexpr int kSliceSums = 1 + kPriceSums;  // the raw terminal sum, then price_kernel's five
+constexpr size_t kSliceScratch = kWaves * kSliceSums * sizeof(double);
+constexpr int kFinishThreads = 256;
+constexpr int kFinishLanes = 8;  // threads per contract in price_finish_kernel (kSliceSums of them add)
+constexpr int kFinishBatch = 32;  // partials a price_finish_kernel thread loads before it adds them in order
+
+template <typename Real, bool LOG_EULER, bool HW, int PASS>
+__global__ __launch_bounds__(kThreads) void price_slice_kernel(EngineArgs a, int64_t slice_paths, int32_t W,
+                                                               double* __restrict__ ws) {
+  extern __shared__ double lds[];  // [kWaves][kSliceSums] reduction scratch
+  if constexpr (sizeof(Real) == 8) math::f64_tables_load();
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x / static_cast<uint32_t>(W);
+  const int64_t w = blockIdx.x % static_cast<uint32_t>(W);
+  const int T = a.T;
+  const int64_t begin = w * slice_paths;  // < P: W = ceil(P / slice_paths)
+  const int64_t end = a.P - begin > slice_paths ? begin + slice_paths : a.P;
+  const Contract c = load_contract(a.contracts + b * 6);
+  const uint64_t ordinal = static_cast<uint64_t>((a.ordinal_dev ? *a.ordinal_dev : 0) + a.ordinal0 + b);
+  const Stepper<Real, LOG_EULER, HW> step(c, T);
+  const Real x0 = static_cast<Real>(c.X0);
+  const PayoffPre<Real> pre(c);
+  double* slot = ws + (b * W + w) * kSliceSums;
+
+  double v[kPriceSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double sum[1] = {0.0};
+  Payoff<Real> pay;
+  if constexpr (PASS == kSliceRaw) pay = Payoff<Real>(a, pre, 1.0);  // a.normalize == 0: scale 1
+  if constexpr (PASS == kSlicePay) pay = Payoff<Real>(a, pre, ws[a.B * W * kSliceSums + b]);
+  for (int64_t chunk = begin; chunk < end; chunk += kChunk) {
+    const int64_t p0 = chunk + kPathsPerLane * static_cast<int64_t>(tid);
+    const int nvalid = static_cast<int>(p0 >= end ? 0 : (end - p0 >= kPathsPerLane ? kPathsPerLane : end - p0));
+    Real xt[kPathsPerLane];
+    if (nvalid > 0) {
+      PathStream s(a.seed, ordinal, static_cast<uint64_t>(p0 / kPathsPerLane), T);
+      double unused = 0.0;
+      lane_rows_s<Real, LOG_EULER, HW, false, false>(s, step, x0, chunk, nullptr, T, 0, unused, xt, tid);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j) xt[j] = Real(0);
+    }
+    if constexpr (PASS != kSlicePay) {
+      Real part = 0;
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j) part += j < nvalid ? xt[j] : Real(0);
+      sum[0] += static_cast<double>(part);
+    }
+    if constexpr (PASS != kSliceSum) {
+#pragma unroll
+      for (int j = 0; j < kPathsPerLane; ++j)
+        if (j < nvalid) price_add(pay, xt[j], v);
+    }
+  }
+  if constexpr (PASS != kSlicePay) {
+    price_reduce(sum, lds);
+    if (tid == 0) slot[0] = sum[0];
+  }
+  if constexpr (PASS != kSliceSum) {
+    price_reduce(v, lds);
+    if (tid == 0) {
+#pragma unroll
+      for (int i = 0; i < kPriceSums; ++i) slot[1 + i] = v[i];
+    }
+  }
+}
+
+// Thread (b, k), k < kSliceSums, adds partial k of contract b over the slices in order.  totals_only: thread (b, 0)
+// leaves the total raw sum in the workspace's totals (between the two NORMALIZE passes); else the 8 columns from
+// the six totals, by thread (b, 0), in price_kernel's closing arithmetic.
+template <typename Real>
+__global__ __launch_bounds__(kFinishThreads) void price_finish_kernel(EngineArgs a, int32_t W, int32_t totals_only,
+                                                                      double* __restrict__ ws,
+                                                                      double* __restrict__ prices) {
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * (kFinishThreads / kFinishLanes) + threadIdx.x / kFinishLanes;
+  const int k = threadIdx.x % kFinishLanes;
+  const bool live = b < a.B;
+  double tot = 0.0;
+  if (live && k < (totals_only ? 1 : kSliceSums)) {
+    const double* part = ws + b * W * kSliceSums + k;
+    tot = part[0];
+    // the adds stay in slice order; the loads of kFinishBatch slices are issued together, so the walk waits on
+    // memory once per batch and not once per slice (W = 512: 16 round trips)
+    int32_t w = 1;
+    for (; w + kFinishBatch <= W; w += kFinishBatch) {
+      double t[kFinishBatch];
+#pragma unroll
+      for (int i = 0; i < kFinishBatch; ++i) t[i] = part[static_cast<int64_t>(w + i) * kSliceSums];
+#pragma unroll
+      for (int i = 0; i < kFinishBatch; ++i) tot += t[i];
+    }
+    for (; w < W; ++w) tot += part[static_cast<int64_t>(w) * kSliceSums];
+  }
+  if (totals_only) {
+    if (live && k == 0) ws[a.B * W * kSliceSums + b] = tot;
+    return;
+  }
+  double v[kSliceSums];  // the contract's six totals, from its kFinishLanes-lane group (every lane takes part)
+  const int base = (threadIdx.x & 63) - k;
+#pragma unroll
+  for (int i = 0; i < kSliceSums; ++i) v[i] = __shfl(tot, base + i, 64);
+  if (live && k == 0) {
+    const PayoffPre<Real> pre(load_contract(a.contracts + b * 6));
+    const double n = static_cast<double>(a.P);
+    const double put = v[1] / n, call = v[2] / n;
+    double put_se = 0.0, call_se = 0.0;
+    if (a.P > 1) {
+      const double pv = v[4] - n * put * put, cv = v[5] - n * call * call;
+      put_se = sqrt((pv > 0.0 ? pv : 0.0) / (n - 1.0) / n);
+      call_se = sqrt((cv > 0.0 ? cv : 0.0) / (n - 1.0) / n);
+    }
+    const Real ip = pre.K - pre.F, ic = pre.F - pre.K;
+    double* out = prices + b * SMC_PRICE_COLS;
+    out[0] = put;
+    out[1] = call;
+    out[2] = v[3] / n;
+    out[3] = put_se;
+    out[4] = call_se;
+    out[5] = static_cast<double>(pre.df * (ip > Real(0) ? ip : Real(0)));
+    out[6] = static_cast<double>(pre.df * (ic > Real(0) ? ic : Real(0)));
+    out[7] = v[0];
+  }
+}
+
 // ---- path-dependent batched pricing: path_price_kernel (smc_gbm_price_paths) --------------------
 // price_kernel's geometry, streams and sum order (one 512-lane workgroup per contract, 4 consecutive paths
 // per lane and 2048-path chunk, no row stored, lanes wholly past P idle), with a per-row hook on the rolled
@@ -3041,6 +3180,61 @@ int32_t launch_price(const EngineArgs& a, int mode, size_t lds, double* prices, 
                    : launch_price_k<Real, false, false>(a, mode, lds, prices, stream);
 }
 
+// Slices per contract of the sliced price call (host only, no HIP call); -1: not a (P, slice_paths) it takes
+int64_t price_slice_count(int64_t P, int64_t slice_paths) {
+  if (P <= 0 || P >= (1LL << 40) || slice_paths <= 0 || slice_paths % kChunk != 0) return -1;
+  const int64_t W = (P + slice_paths - 1) / slice_paths;
+  return W > 65535 ? -1 : W;
+}
+
+// The default slice length: two workgroups on each of 256 CUs per contract, in whole chunks; from P alone, so the
+// block a default call gives does not change with the batch size or the device
+constexpr int64_t kSliceTarget = 512;
+int64_t price_slice_default(int64_t P) {
+  if (P <= 0 || P >= (1LL << 40)) return -1;
+  const int64_t per = kChunk * kSliceTarget;
+  const int64_t chunks = (P + per - 1) / per;
+  return kChunk * (chunks > 1 ? chunks : 1);
+}
+
+// The two (RAW) or four (NORMALIZE) launches of the sliced price call, in stream order
+template <typename Real, bool LOG_EULER, bool HW>
+int32_t launch_price_sliced_k(const EngineArgs& a, int64_t slice_paths, int32_t W, double* ws, double* prices,
+                              hipStream_t stream) {
+  const dim3 grid(static_cast<unsigned>(a.B * W)), block(kThreads);
+  constexpr int kPerBlock = kFinishThreads / kFinishLanes;
+  const dim3 fgrid(static_cast<unsigned>((a.B + kPerBlock - 1) / kPerBlock)), fblock(kFinishThreads);
+  const uint32_t lds = static_cast<uint32_t>(kSliceScratch);
+  if (!a.normalize) {
+    launch(price_slice_kernel<Real, LOG_EULER, HW, kSliceRaw>, grid, block, lds, stream, a, slice_paths, W, ws);
+    if (int32_t st = check_launch("price_slice_kernel")) return st;
+  } else {
+    launch(price_slice_kernel<Real, LOG_EULER, HW, kSliceSum>, grid, block, lds, stream, a, slice_paths, W, ws);
+    if (int32_t st = check_launch("price_slice_kernel")) return st;
+    launch(price_finish_kernel<Real>, fgrid, fblock, 0, stream, a, W, 1, ws, prices);
+    if (int32_t st = check_launch("price_finish_kernel")) return st;
+    launch(price_slice_kernel<Real, LOG_EULER, HW, kSlicePay>, grid, block, lds, stream, a, slice_paths, W, ws);
+    if (int32_t st = check_launch("price_slice_kernel")) return st;
+  }
+  launch(price_finish_kernel<Real>, fgrid, fblock, 0, stream, a, W, 0, ws, prices);
+  return check_launch("price_finish_kernel");
+}
+
+template <typename Real>
+int32_t launch_price_sliced(const EngineArgs& a, int64_t slice_paths, int32_t W, double* ws, double* prices,
+                            hipStream_t stream) {
+  const bool log_euler = (a.scheme & 0xff) == SMC_SCHEME_LOG_EULER;
+  const bool hw = (a.scheme & SMC_MATH_HW) != 0;
+  if constexpr (sizeof(Real) == 4) {
+    if (hw) {
+      return log_euler ? launch_price_sliced_k<Real, true, true>(a, slice_paths, W, ws, prices, stream)
+                       : launch_price_sliced_k<Real, false, true>(a, slice_paths, W, ws, prices, stream);
+    }
+  }
+  return log_euler ? launch_price_sliced_k<Real, true, false>(a, slice_paths, W, ws, prices, stream)
+                   : launch_price_sliced_k<Real, false, false>(a, slice_paths, W, ws, prices, stream);
+}
+
 // path_price_kernel's plan for a shape (host only, no HIP call): 0 one RAW pass, 1 the NORMALIZE replay, -1 not
 // a flag set it takes, -2 more time steps than LDS holds scales for.  NORMALIZE: *rows is the even number of
 // accumulator rows per sweep (T rounded up to even where that fits), *lds the dynamic LDS.
@@ -3552,6 +3746,70 @@ const char* smc_gbm_price_kernel(int32_t timesteps, int64_t n_paths, int32_t sch
     case kPriceReplay: return "price_kernel(replay)";
     default: return "unsupported";
   }
+}
+
+int32_t smc_gbm_price_sliced(const double* contracts_dev, int64_t n_contracts, int32_t timesteps, int64_t n_paths,
+                             int64_t slice_paths, uint64_t mc_seed, const int64_t* ordinal_dev, int64_t ordinal0,
+                             int32_t scheme, int32_t normalization, int32_t dtype, double* prices_dev,
+                             void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  constexpr int32_t kNoMode = SMC_PRICE_REPLAY | SMC_TRAIN_DYNAMIC;
+  if (int32_t st = validate_common(contracts_dev, n_contracts, timesteps, n_paths, dtype)) return st;
+  if (!prices_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_sliced: prices_dev is NULL");
+  if (!valid_scheme(scheme & ~kNoMode)) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_sliced: bad scheme");
+  if (scheme & SMC_MATH_REF)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_gbm_price_sliced: SMC_MATH_REF is for smc_train_targets / smc_train_step");
+  if ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_sliced: SMC_MATH_HW is f32 only");
+  if (normalization != SMC_NORM_RAW && normalization != SMC_NORM_NORMALIZE)
+    return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_sliced: bad normalization");
+  if (scheme & kNoMode)
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_gbm_price_sliced: SMC_PRICE_REPLAY / SMC_TRAIN_DYNAMIC do not apply (there is no mode to force)");
+  if (slice_paths <= 0 || slice_paths % kChunk != 0)
+    return fail(SMC_ERR_INVALID_SHAPE, "smc_gbm_price_sliced: slice_paths must be a positive multiple of 2048");
+  const int64_t W = price_slice_count(n_paths, slice_paths);
+  if (W < 0 || n_contracts * W >= (1LL << 31))
+    return fail(SMC_ERR_INVALID_SHAPE,
+                "smc_gbm_price_sliced: more than 65,535 slices per contract, or 2^31 or more workgroups");
+  if (!workspace_dev) return fail(SMC_ERR_INVALID_ARGUMENT, "smc_gbm_price_sliced: workspace_dev is NULL");
+  if (workspace_bytes < smc_gbm_price_sliced_workspace_bytes(n_contracts, n_paths, slice_paths))
+    return fail(SMC_ERR_INVALID_ARGUMENT,
+                "smc_gbm_price_sliced: workspace_bytes below smc_gbm_price_sliced_workspace_bytes");
+  if (n_contracts == 0) return SMC_OK;
+  EngineArgs a{};
+  a.contracts = contracts_dev;
+  a.B = n_contracts;
+  a.T = timesteps;
+  a.P = n_paths;
+  a.seed = mc_seed;
+  a.ordinal_dev = ordinal_dev;
+  a.ordinal0 = ordinal0;
+  a.scheme = scheme;
+  a.normalize = normalization != SMC_NORM_RAW;
+  double* ws = static_cast<double*>(workspace_dev);
+  return dtype == SMC_DTYPE_F32
+             ? launch_price_sliced<float>(a, slice_paths, static_cast<int32_t>(W), ws, prices_dev, as_stream(stream))
+             : launch_price_sliced<double>(a, slice_paths, static_cast<int32_t>(W), ws, prices_dev, as_stream(stream));
+}
+
+int64_t smc_gbm_price_sliced_workspace_bytes(int64_t n_contracts, int64_t n_paths, int64_t slice_paths) {
+  const int64_t W = price_slice_count(n_paths, slice_paths);
+  if (n_contracts < 0 || n_contracts > 0x7fffffffLL || W < 0 || n_contracts * W >= (1LL << 31)) return -1;
+  return static_cast<int64_t>(sizeof(double)) * n_contracts * (kSliceSums * W + 1);
+}
+
+int64_t smc_gbm_price_slice_paths(int64_t n_paths) { return price_slice_default(n_paths); }
+
+const char* smc_gbm_price_sliced_kernel(int32_t timesteps, int64_t n_paths, int64_t slice_paths, int32_t scheme,
+                                        int32_t normalization, int32_t dtype) {
+  if (timesteps <= 0 || price_slice_count(n_paths, slice_paths) < 0 || !valid_scheme(scheme) ||
+      (scheme & SMC_MATH_REF) || (dtype != SMC_DTYPE_F32 && dtype != SMC_DTYPE_F64) ||
+      ((scheme & SMC_MATH_HW) && dtype == SMC_DTYPE_F64))
+    return "unsupported";
+  if (normalization == SMC_NORM_RAW) return "price_slice_kernel(raw)";
+  if (normalization == SMC_NORM_NORMALIZE) return "price_slice_kernel(replay)";
+  return "unsupported";
 }
 
 int32_t smc_gbm_price_paths(const double* contracts_dev, const double* barriers_dev, int64_t n_contracts,
