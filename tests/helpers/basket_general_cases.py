@@ -18,6 +18,11 @@ ORD0 = 3
 # (A, T, P, normalize, B): lds with two chunks, odd A, A = 8, a partial chunk, RAW, replay by itself
 CASES = [(4, 16, 4096, 1, 6), (3, 5, 2048, 1, 6), (8, 2, 2048, 1, 6), (2, 4, 693, 1, 6), (5, 3, 1000, 0, 6),
          (2, 3, 65536, 1, 3)]
+# every other (A, normalisation), at the smallest shape that still runs the park block and the normalisation sweep
+# (one stream per group, a ragged lane, a partial chunk): tests/test_instantiation_ledger.py holds the table to the
+# ledger of instantiations, and each row below is the only one of its (A, normalisation)
+LEDGER_CASES = [(A, 3, 693, 1, 3) for A in (1, 5, 6, 7)] + [(A, 3, 693, 0, 3) for A in (1, 2, 3, 4, 6, 7, 8)]
+CASES += LEDGER_CASES
 
 
 def sobol_rows(oracle, A: int, n: int, skip: int = 0) -> np.ndarray:

@@ -32,6 +32,13 @@ REFERENCE_CASES = [
     ("spread", 2, 3, 2049, 1, 4),
     ("spread", 2, 3, 2047, 0, 4),
 ]
+# every other (A, normalisation), at the smallest shape that still runs the pass plan and the pair columns of its A, the
+# park block and the normalisation sweep (one stream per group, a ragged lane, a partial chunk):
+# tests/test_instantiation_ledger.py holds the table to the ledger of instantiations, and each row below is the only one
+# of its (A, normalisation)
+LEDGER_CASES = ([("drawn", A, 3, 693, 1, 3) for A in (1, 4, 6, 7)]
+                + [("drawn", A, 3, 693, 0, 3) for A in (3, 4, 6, 7, 8)])
+REFERENCE_CASES += LEDGER_CASES
 
 # The largest departure of the float32 restatement (tests/helpers/basket_general_greeks_restate.py: portable math, a
 # float32 walk of the step with the general factor) from the float64 reference over REFERENCE_CASES, as a share of the

@@ -28,6 +28,11 @@ CASES = [
 # (A, T, P, norm, B) of the comparison with the float64 reference: the shapes above on Sobol-drawn contracts
 REFERENCE_CASES = [(4, 16, 4096, 1, 6), (3, 5, 2048, 1, 6), (1, 3, 2048, 0, 6), (8, 2, 2048, 1, 6), (2, 4, 693, 1, 6),
                    (4, 1, 528, 0, 6), (2, 3, 65536, 1, 3)]
+# every other (A, normalisation), at the smallest shape that still runs the pass plan of its A, the park block and the
+# normalisation sweep (one stream per group, a ragged lane, a partial chunk): tests/test_instantiation_ledger.py holds
+# the table to the ledger of instantiations, and each row below is the only one of its (A, normalisation)
+LEDGER_CASES = [(A, 3, 693, 1, 3) for A in (1, 5, 6, 7)] + [(A, 3, 693, 0, 3) for A in (2, 3, 5, 6, 7, 8)]
+REFERENCE_CASES += LEDGER_CASES
 
 # The largest departure of the float32 restatement (portable math, the oracle's kernel-mode terminal values) from the
 # float64 reference over REFERENCE_CASES, as a share of the column's own standard error: measured 1.11e-3 (theta call of

@@ -18,6 +18,11 @@ SEED, ORD0 = cases.SEED, cases.ORD0
 # (A, T, P, B): two sweeps (64 row sums), odd A, A = 8 in column groups, three sweeps (80 row sums) with a partial
 # last lane, A = 5 in column groups with a partial chunk
 CASES = [(4, 16, 4096, 6), (3, 5, 2048, 6), (8, 2, 2048, 6), (2, 40, 693, 4), (5, 3, 1000, 6)]
+# the asset counts those leave out, at the smallest shape that still runs the column groups and the normalisation sweep
+# (one stream per group, a ragged lane, a partial chunk): tests/test_instantiation_ledger.py holds the table to the
+# ledger of instantiations, and each row below is the only one of its A
+LEDGER_CASES = [(1, 3, 693, 3), (6, 3, 693, 3), (7, 3, 693, 3)]
+CASES += LEDGER_CASES
 SPREAD = (2, 4, 2049, 6)  # weights (1, -1), K = 0: levels of either sign
 EPS = {"portable": br.PORTABLE, "hw": br.HW}
 

@@ -1,7 +1,9 @@
-"""The ledger of training-kernel instantiations: every template instantiation the host code of csrc/gbm.hip
+"""The ledger of kernel instantiations: every template instantiation the host code of csrc/gbm.hip
 (launch_engine<float>, launch_engine<double>) and csrc/basket.hip (launch_basket_k, launch_basket_resident_k) can
-select, written out literally, and the host rules that map a row of a reference test's case table to the one it
-runs.  tests/test_instantiation_ledger.py holds the ledger to the source text and the case tables to the ledger: the
+select for training, and (second half of the file: ALL_GBM_PRICING, ALL_BASKET_PRICING, pricing_runs_of) every one the
+batched pricing and Greeks entries can select, written out literally, and the host rules that map a row of a
+reference test's case table to the ones it runs.
+tests/test_instantiation_ledger.py holds the ledger to the source text and the case tables to the ledger: the
 unit that can be wrong in this code base is the instantiation, so every reachable one has to have
 a case in the float64-reference files.  No GPU, no library: plain Python.
 
@@ -257,3 +259,201 @@ UNREACHABLE: dict[tuple, str] = {
         f"basket_res_slices returns 0: basket_resident_lds_bytes({A}, N) = {basket_resident_lds_bytes(A)} > 160 KiB for "
         "every N, so smc_basket_train_targets launches basket_kernel"
     for A, m, st in product((7, 8), MATHS, STORES)}
+
+
+# ---- the batched pricing and Greeks kernels --------------------------------------------------------------------------
+# A single-asset pricing tuple is (kernel, dtype, scheme, math, mode): scheme "" for the Greeks kernels (log-Euler
+# only) and for price_finish_kernel<Real>; mode is the MODE argument "raw" / "lds" / "replay" (price_kernel,
+# greeks_kernel), the PASS argument "Raw" / "Sum" / "Pay" (price_slice_kernel), the NORMALIZE argument "RAW" /
+# "NORMALIZE" (path_price_kernel, path_greeks_kernel), "" for price_finish_kernel.  A basket pricing tuple is
+# (kernel, A, math, mode) with the same words.
+PRICE_MODES = ("raw", "lds", "replay")
+SLICE_PASSES = ("Raw", "Sum", "Pay")
+NORMS = ("RAW", "NORMALIZE")
+# (dtype, math) of launch_price<Real> and its kin: the HW lines stand under if constexpr (sizeof(Real) == 4)
+TYPINGS = (("f32", "portable"), ("f32", "hw"), ("f64", "portable"))
+
+ALL_GBM_PRICING: frozenset[tuple] = frozenset(
+    # launch_price_k<Real, LOG_EULER, HW> x its ternary over kPriceRaw / kPriceLds / kPriceReplay
+    [("price_kernel", d, s, m, mode) for (d, m), s, mode in product(TYPINGS, SCHEMES, PRICE_MODES)]
+    # launch_price_sliced_k<Real, LOG_EULER, HW>: kSliceRaw, or kSliceSum and kSlicePay, and price_finish_kernel<Real>
+    + [("price_slice_kernel", d, s, m, ps) for (d, m), s, ps in product(TYPINGS, SCHEMES, SLICE_PASSES)]
+    + [("price_finish_kernel", d, "", "portable", "") for d in ("f32", "f64")]
+    # launch_path_price_k<Real, LOG_EULER, HW> x a.normalize
+    + [("path_price_kernel", d, s, m, n) for (d, m), s, n in product(TYPINGS, SCHEMES, NORMS)]
+    # launch_greeks_k<Real, HW> x its ternary over the three modes; launch_path_greeks_k<Real, HW> x a.normalize
+    + [("greeks_kernel", d, "", m, mode) for (d, m), mode in product(TYPINGS, PRICE_MODES)]
+    + [("path_greeks_kernel", d, "", m, n) for (d, m), n in product(TYPINGS, NORMS)])
+
+PARK_KERNELS = ("basket_price_kernel", "basket_general_kernel", "basket_greeks_kernel", "basket_greeks_general_kernel")
+BASKET_PATH_KERNELS = ("basket_path_kernel", "basket_path_greeks_kernel")
+ALL_BASKET_PRICING: frozenset[tuple] = frozenset(
+    # launch_parked: with_variant (A = 1..8, HW) x with_price_mode, for each pick(A, HW, MODE) caller
+    [(k, A, m, mode) for k, A, m, mode in product(PARK_KERNELS, range(1, MAX_ASSETS + 1), MATHS, PRICE_MODES)]
+    # with_variant x with_flag(a.normalize)
+    + [(k, A, m, n) for k, A, m, n in product(BASKET_PATH_KERNELS, range(1, MAX_ASSETS + 1), MATHS, NORMS)])
+
+# No host rule keeps a pricing or Greeks instantiation out: SMC_PRICE_REPLAY reaches replay at any P, and the parked
+# block of P = 693 paths fits for every A.
+UNREACHABLE_PRICING: dict[tuple, str] = {}
+
+# ---- the park rule: price_mode / greeks_mode (gbm.hip) and basket_park_mode (basket.hip) ----
+PRICE_PARK_BYTES = 144 * 1024      # SMC_PRICE_PARK_BYTES in both files
+K_MAX_LDS = 160 * 1024             # kMaxLds
+K_PRICE_SCRATCH = 8 * 5 * 8        # kPriceScratch = kWaves * kPriceSums * sizeof(double)
+F64_TABLE_BYTES = 51232            # sizeof(math::F64Tables): the static LDS image of the f64 path math
+K_B_WAVES = 8                      # kBWaves = kBThreads / 64
+
+
+def _greek_terms(A: int) -> int:   # basket_greek_terms
+    return 4 * A + 8
+
+
+def _ggreek_terms(A: int) -> int:  # basket_ggreek_terms
+    return 4 * A + 6 + A * (A - 1)
+
+
+_M = MAX_ASSETS
+K_B_PRICE_HEAD = K_B_WAVES * 16 + _M * _M + K_B_WAVES * _M + _M                      # kBPriceHead, kBPriceSums = 16
+K_B_GREEK_HEAD = (K_B_WAVES * 2 * _greek_terms(4) + 3 * _M * _M + K_B_WAVES * 3 * _M + 3 * _M
+                  + (_M * 8 + _M * _M) // 2)                                         # kBGreekHead, kBGreekFc = 8
+_GG_SUMS = _M + _M * (_M + 1) // 2                                                   # kBGGSums
+K_B_GG_HEAD = (K_B_WAVES * 2 * _ggreek_terms(3) + _M * _M + K_B_WAVES * _GG_SUMS + _GG_SUMS
+               + (_M * 8 + (_M * (_M - 1) // 2) * (_M * _M + 2 * _M)) // 2)          # kBGGHead, kBGGFc = 8
+# the scratch member of each ParkKernel constant, in bytes
+PARK_SCRATCH = {"basket_price_kernel": 8 * K_B_PRICE_HEAD, "basket_general_kernel": 8 * K_B_PRICE_HEAD,
+                "basket_greeks_kernel": 8 * K_B_GREEK_HEAD, "basket_greeks_general_kernel": 8 * K_B_GG_HEAD}
+
+
+def price_mode(P: int, dtype: str, normalize: bool, force_replay: bool = False) -> str:
+    """price_mode and greeks_mode of gbm.hip: the scratch and the terminal row of P Reals (padded to 8 B) are parked
+    while they fit SMC_PRICE_PARK_BYTES and, beside the f64 kernels' static tables, a CU's LDS."""
+    if not normalize:
+        return "raw"
+    if force_replay:
+        return "replay"
+    esz, fixed = (8, F64_TABLE_BYTES) if dtype == "f64" else (4, 0)
+    park = K_PRICE_SCRATCH + (P * esz + 7) // 8 * 8
+    return "replay" if park > PRICE_PARK_BYTES or park + fixed > K_MAX_LDS else "lds"
+
+
+def basket_park_mode(kernel: str, A: int, P: int, normalize: bool, force_replay: bool = False) -> str:
+    """basket_park_mode of basket.hip: the kernel's scratch and [A][P rounded up to 4] floats against kBPriceParkBytes."""
+    if not normalize:
+        return "raw"
+    if force_replay:
+        return "replay"
+    return "replay" if PARK_SCRATCH[kernel] + A * ((P + 3) // 4 * 4) * 4 > PRICE_PARK_BYTES else "lds"
+
+
+def sliced_launches(dtype: str, scheme: str, math: str, normalize: bool) -> list[tuple]:
+    """launch_price_sliced_k's launches in stream order: RAW runs Raw then finish; NORMALIZE runs Sum, finish (totals
+    only), Pay, finish."""
+    finish = ("price_finish_kernel", dtype, "", "portable", "")
+    if not normalize:
+        return [("price_slice_kernel", dtype, scheme, math, "Raw"), finish]
+    return [("price_slice_kernel", dtype, scheme, math, "Sum"), finish,
+            ("price_slice_kernel", dtype, scheme, math, "Pay"), finish]
+
+
+@dataclass(frozen=True)
+class Run:
+    """One launch (one call, for the sliced entry) a reference test makes for a case row and holds to the float64
+    reference: the instantiations it runs (the first is the one the name query reports), the flags of the call and
+    the name its smc_*_kernel query must give."""
+    insts: tuple[tuple, ...]
+    math: str          # "portable" / "hw"
+    dtype: str         # "f32" / "f64" (basket: "f32")
+    normalize: bool
+    force_replay: bool  # SMC_PRICE_REPLAY set in the call
+    name: str
+
+
+def _park_run(kernel: str, A: int, P: int, math: str, normalize: bool, force: bool) -> Run:
+    mode = basket_park_mode(kernel, A, P, normalize, force)
+    return Run(((kernel, A, math, mode),), math, "f32", normalize, force, f"{kernel}({mode})")
+
+
+def park_runs(kernel: str, A: int, P: int, normalize: bool, maths: tuple[str, ...] = MATHS) -> list[Run]:
+    """Both maths; the mode the shape selects and, where that is lds, SMC_PRICE_REPLAY's replay as well."""
+    out = []
+    for m in maths:
+        out.append(_park_run(kernel, A, P, m, normalize, False))
+        if out[-1].insts[0][3] == "lds":
+            out.append(_park_run(kernel, A, P, m, normalize, True))
+    return out
+
+
+def _basket_path_runs(kernel: str, A: int) -> list[Run]:
+    return [Run(((kernel, A, m, NORMS[n]),), m, "f32", bool(n), False, f"{kernel}({'replay' if n else 'raw'})")
+            for m in MATHS for n in (1, 0)]
+
+
+def _price_runs(kernel: str, dtype: str, scheme: str, P: int, maths: tuple[str, ...], norms=(False, True)) -> list[Run]:
+    """price_kernel / greeks_kernel: per math raw, the mode the shape selects and, where that is lds, forced replay."""
+    out = []
+    for m in maths:
+        for normalize in norms:
+            for force in ((False, True) if normalize and price_mode(P, dtype, True) == "lds" else (False,)):
+                mode = price_mode(P, dtype, normalize, force)
+                out.append(Run(((kernel, dtype, scheme, m, mode),), m, dtype, normalize, force, f"{kernel}({mode})"))
+    return out
+
+
+def _path_runs(kernel: str, dtype: str, scheme: str, maths: tuple[str, ...], norms=(False, True)) -> list[Run]:
+    return [Run(((kernel, dtype, scheme, m, NORMS[n]),), m, dtype, n, False, f"{kernel}({'replay' if n else 'raw'})")
+            for m in maths for n in norms]
+
+
+def _sliced_runs(dtype: str, scheme: str, maths: tuple[str, ...]) -> list[Run]:
+    return [Run(tuple(sliced_launches(dtype, scheme, m, n)), m, dtype, n, False,
+                f"price_slice_kernel({'replay' if n else 'raw'})") for m in maths for n in (False, True)]
+
+
+def pricing_runs_of(table: str, case: tuple) -> list[Run]:
+    """Every launch the reference test of the table makes for the case row.  The GPU tests take their loops from here,
+    so a row cannot claim an instantiation its test does not launch and compare.  Tables:
+    basket price (A, T, P, B)                 PRICE_CASES of tests/test_gpu_basket_reference.py, both normalisations
+    basket general (A, T, P, norm, B)         basket_general_cases.CASES
+    basket greeks (A, T, P, norm, B)          basket_greeks_cases.REFERENCE_CASES
+    basket general greeks (kind, A, T, P, norm, B)  basket_general_greeks_cases.REFERENCE_CASES
+    basket path, basket path greeks (A, T, P, B)    basket_path_cases.CASES, basket_path_greeks_cases.CASES
+    price f32, path price f32 (T, P, scheme)  PRICE_CASES of tests/test_gpu_gbm_reference.py
+    price f64, path price f64 (T, P, scheme)  F64_PRICE_CASES, F64_PATH_PRICE_CASES of test_gpu_gbm_typing_reference.py
+    greeks f32 (mode, B, T, P, force_replay)  CASES of tests/test_gpu_greeks_reference.py; greeks f64 (T, P) F64_CASES
+    path greeks (math, T, P)                  SHAPE_CASES of tests/test_gpu_path_greeks_reference.py
+    sliced f32 (T, P, span, scheme), sliced f64 (T, P, span, scheme)  of tests/test_gpu_price_sliced.py"""
+    if table == "basket price":
+        A, _, P, _ = case
+        return [r for n in (False, True) for r in park_runs("basket_price_kernel", A, P, n)]
+    if table in ("basket general", "basket greeks"):
+        A, _, P, norm, _ = case
+        return park_runs("basket_general_kernel" if table == "basket general" else "basket_greeks_kernel", A, P, bool(norm))
+    if table == "basket general greeks":
+        _, A, _, P, norm, _ = case
+        return park_runs("basket_greeks_general_kernel", A, P, bool(norm))
+    if table == "basket path":
+        return _basket_path_runs("basket_path_kernel", case[0])
+    if table == "basket path greeks":
+        return _basket_path_runs("basket_path_greeks_kernel", case[0])
+    if table in ("price f32", "price f64"):
+        _, P, scheme = case
+        d = table[-3:]
+        return _price_runs("price_kernel", d, _SCHEME[scheme], P, MATHS if d == "f32" else ("portable",))
+    if table in ("path price f32", "path price f64"):
+        d = table[-3:]
+        return _path_runs("path_price_kernel", d, _SCHEME[case[2]], MATHS if d == "f32" else ("portable",))
+    if table == "greeks f32":
+        mode, _, _, P, force = case
+        normalize = mode != "raw"
+        return [Run((("greeks_kernel", "f32", "", m, price_mode(P, "f32", normalize, bool(force))),), m, "f32", normalize,
+                    bool(force), f"greeks_kernel({price_mode(P, 'f32', normalize, bool(force))})") for m in MATHS]
+    if table == "greeks f64":
+        return _price_runs("greeks_kernel", "f64", "", case[1], ("portable",))
+    if table == "path greeks":
+        math = case[0]
+        return _path_runs("path_greeks_kernel", "f64" if math == "f64" else "f32", "", ("portable" if math == "f64" else math,))
+    if table in ("sliced f32", "sliced f64"):
+        d = table[-3:]
+        return _sliced_runs(d, _SCHEME[case[3]], MATHS if d == "f32" else ("portable",))
+    raise AssertionError(table)

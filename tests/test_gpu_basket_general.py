@@ -21,6 +21,7 @@ from spectralmc_amd.basket import BasketConfig, BasketEngine, basket_price, pack
 from tests.helpers import basket_general_cases as cases
 from tests.helpers import basket_general_reference as gr
 from tests.helpers import basket_reference as br
+from tests.helpers import instantiations as inst
 from tests.helpers import poisoned
 
 pytestmark = pytest.mark.gpu
@@ -92,14 +93,16 @@ def _drawn(A: int, B: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
 
 def _against_reference(rows, w, C, A, T, P, norm, label) -> None:
     tri = cases.pack(C)
-    for math, (eps, hw) in MATHS.items():
-        ref = gr.reference(_oracle, rows, A, T, P, SEED, ORD0, weights=w, corr=C, normalize=bool(norm), eps=eps)
-        assert br.exercise_count_ok(ref.doubt, P), ref.doubt  # before the kernel's output is looked at
-        modes = {_name(A, T, P, hw, norm): hw}
-        if norm:
-            modes[_name(A, T, P, hw | _lib.PRICE_REPLAY, norm)] = hw | _lib.PRICE_REPLAY
-        for mode, flags in modes.items():
-            _check(_general(rows, A, T, P, flags, norm, w=w, tri=tri), ref, f"{label} {math} {mode}")
+    refs = {}
+    # every launch the ledger counts for the row: both maths, the mode the shape selects and forced replay beside lds
+    for run in inst.pricing_runs_of("basket general", (A, T, P, norm, rows.shape[0])):
+        eps, hw = MATHS[run.math]
+        if run.math not in refs:
+            refs[run.math] = gr.reference(_oracle, rows, A, T, P, SEED, ORD0, weights=w, corr=C, normalize=bool(norm), eps=eps)
+            assert br.exercise_count_ok(refs[run.math].doubt, P), refs[run.math].doubt  # before the kernel's output
+        flags = hw | (_lib.PRICE_REPLAY if run.force_replay else 0)
+        assert _name(A, T, P, flags, norm) == run.name and run.normalize == bool(norm)
+        _check(_general(rows, A, T, P, flags, norm, w=w, tri=tri), refs[run.math], f"{label} {run.math} {run.name}")
 
 
 # ---- against the float64 reference -----------------------------------------------------------------------------------

@@ -9,7 +9,8 @@ run to run, under a split of the batch, the ordinal on the host or on the device
 an all-rho table against none, the delta, vega, rho and theta columns against smc_basket_greeks at A in {1, 2, 4, 8});
 the pair columns against smc_basket_greeks's correlation column; Margrabe's closed form; the conventions; the Python
 surface; a replayed graph.  Smallest shapes that reach every path: B = 3..6, T in {1, 3, 16}, A in {1, 2, 3, 5, 8},
-P in {1, 5, 2047, 2049} and one P on each side of the parking bound at A = 8."""
+P in {1, 5, 2047, 2049} and one P on each side of the parking bound at A = 8; the reference cases also hold every
+other (A, normalisation) at T = 3, P = 693, so that every instantiation is compared (tests/test_instantiation_ledger.py)."""
 
 from __future__ import annotations
 
@@ -30,6 +31,7 @@ from tests.helpers import basket_general_greeks_cases as cases
 from tests.helpers import basket_general_greeks_reference as gg
 from tests.helpers import basket_greeks_cases as eq_cases
 from tests.helpers import basket_reference as br
+from tests.helpers import instantiations as inst
 
 pytestmark = pytest.mark.gpu
 
@@ -119,9 +121,12 @@ def test_every_column_within_the_allowed_share_of_the_reference(kind, A, T, P, n
     want_mode = "raw" if not norm else ("replay" if (A, P) == (8, cases.PARK_FIRST_REPLAY) else "lds")
     assert _name(A, T, P, 0, norm) == f"basket_greeks_general_kernel({want_mode})"
     worst = {}
-    for math_ in (0, HW, REPLAY, HW | REPLAY):
-        if (math_ & REPLAY) and want_mode != "lds":
-            continue  # raw has no second mode, and the replay case runs replay by itself
+    # every launch the ledger counts for the row (raw has no second mode, and the replay case runs replay by itself)
+    runs = inst.pricing_runs_of("basket general greeks", (kind, A, T, P, norm, B))
+    assert len(runs) == (4 if want_mode == "lds" else 2) and all(r.normalize == bool(norm) for r in runs)
+    for run in runs:
+        math_ = (HW if run.math == "hw" else 0) | (REPLAY if run.force_replay else 0)
+        assert _name(A, T, P, math_, norm) == run.name
         got, _ = _greeks(rows, A, T, P, math_, norm, w=w, tri=tri)
         assert got.shape == ref.shape and not np.isnan(got).any()
         shares = cases.shares_of_stderr(got, ref, rows, A)

@@ -24,6 +24,7 @@ from tests.helpers import basket_greeks_cases as cases
 from tests.helpers import basket_greeks_reference as gr
 from tests.helpers import basket_greeks_restate as rs
 from tests.helpers import basket_reference as br
+from tests.helpers import instantiations as inst
 
 pytestmark = pytest.mark.gpu
 
@@ -285,29 +286,34 @@ def test_basket_greeks_against_the_float64_reference(A, T, P, norm, B, math) -> 
     full = br.reference(_oracle, rows, A, T, P, SEED, ORD0, normalize=bool(norm))
     assert br.exercise_count_ok(full.doubt, P), full.doubt
     ref, ref_sums = gr.greeks(_oracle, rows, A, T, P, SEED, ORD0, normalize=bool(norm))
-    got, sums = _greeks(rows, A, T, P, _lib.MATH_HW if math == "hw" else 0, norm)
-    assert not np.isnan(got).any() and not np.isnan(sums).any()
-    shares = cases.shares_of_stderr(got, ref, rows, A)
-    col = max(shares, key=shares.get)
-    print(f"A {A} T {T} P {P} norm {norm} {math}: largest share of a standard error {shares[col]:.3e} (column {col}); "
-          f"allowed {cases.ALLOWED_SHARE:.3e}")
-    assert shares[col] <= cases.ALLOWED_SHARE, shares
-    n = 4 * A + 6
-    for col in gr.mean_columns(A):
-        se = gr.stderr_column(A, col)
-        if col in (4 * A, 4 * A + 1):  # a constant column's error is rounding noise in both
-            live = ref[:, se] > 1e-9 * np.abs(ref[:, col])
-        else:
-            live = np.ones(B, dtype=bool)
-        np.testing.assert_allclose(got[live, se], ref[live, se], rtol=2 * cases.ALLOWED_SHARE, atol=0, err_msg=str(se))
-    # the terminal sums within basket_reference's a-priori bound, the other two relative to the sums of magnitudes
     eps = br.HW if math == "hw" else br.PORTABLE
     bound = br.reference(_oracle, rows, A, T, P, SEED, ORD0, normalize=bool(norm), eps=eps)
-    assert br.share_used(sums[:, 0], bound.tot, bound.tot_bound) < 1.0
     np.testing.assert_allclose(ref_sums[:, 0], bound.tot, rtol=1e-12, atol=0)
-    if norm:
-        scale = np.abs(ref_sums[:, 0]) * (1.0 + np.abs(np.log(bound.xT / rows[:, 4:4 + A, None])).max(axis=2))
-        assert np.all(np.abs(sums[:, 1] - ref_sums[:, 1]) <= 1e-4 * scale)
+    # every launch the ledger counts for the row in this math: the mode the shape selects and forced replay beside lds
+    runs = [r for r in inst.pricing_runs_of("basket greeks", (A, T, P, norm, B)) if r.math == math]
+    assert runs and all(r.normalize == bool(norm) for r in runs)
+    for run in runs:
+        flags = (_lib.MATH_HW if math == "hw" else 0) | (REPLAY if run.force_replay else 0)
+        assert _name(A, T, P, flags, norm) == run.name
+        got, sums = _greeks(rows, A, T, P, flags, norm)
+        assert not np.isnan(got).any() and not np.isnan(sums).any()
+        shares = cases.shares_of_stderr(got, ref, rows, A)
+        col = max(shares, key=shares.get)
+        print(f"A {A} T {T} P {P} norm {norm} {math} {run.name}: largest share of a standard error {shares[col]:.3e} "
+              f"(column {col}); allowed {cases.ALLOWED_SHARE:.3e}")
+        assert shares[col] <= cases.ALLOWED_SHARE, shares
+        for col in gr.mean_columns(A):
+            se = gr.stderr_column(A, col)
+            if col in (4 * A, 4 * A + 1):  # a constant column's error is rounding noise in both
+                live = ref[:, se] > 1e-9 * np.abs(ref[:, col])
+            else:
+                live = np.ones(B, dtype=bool)
+            np.testing.assert_allclose(got[live, se], ref[live, se], rtol=2 * cases.ALLOWED_SHARE, atol=0, err_msg=str(se))
+        # the terminal sums within basket_reference's a-priori bound, the other two relative to the sums of magnitudes
+        assert br.share_used(sums[:, 0], bound.tot, bound.tot_bound) < 1.0
+        if norm:
+            scale = np.abs(ref_sums[:, 0]) * (1.0 + np.abs(np.log(bound.xT / rows[:, 4:4 + A, None])).max(axis=2))
+            assert np.all(np.abs(sums[:, 1] - ref_sums[:, 1]) <= 1e-4 * scale)
 
 
 # --------------------------------------------------------------------------- 7. hardware math

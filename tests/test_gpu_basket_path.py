@@ -22,6 +22,7 @@ from tests.helpers import basket_general_cases as cases
 from tests.helpers import basket_path_cases as pc
 from tests.helpers import basket_path_reference as pr
 from tests.helpers import basket_reference as br
+from tests.helpers import instantiations as inst
 
 pytestmark = pytest.mark.gpu
 
@@ -90,14 +91,16 @@ def _check(got: tuple[np.ndarray, np.ndarray], ref: pr.PathRef, label: str) -> N
 def _against_reference(case, spread: bool) -> None:
     A, T, P, B = case
     rows, w, C, bars = pc.inputs(_oracle, A, B, spread)
-    tri = cases.pack(C)
-    for math, hw in MATHS.items():
-        for norm in (NORM, RAW):
-            ref = pc.reference(_oracle, A, T, P, B, math, bool(norm), spread)
-            # the condition on the inputs, before the kernel's output is looked at
-            assert pr.count_ok(ref.doubt[:, 0], P) and pr.count_ok(ref.doubt[:, 1], P), ref.doubt
-            got = _paths(rows, A, T, P, hw, norm, w=w, tri=tri, bars=bars)
-            _check(got, ref, f"paths A {A} T {T} P {P} {math} {'NORMALIZE' if norm else 'RAW'}")
+    tri = cases.pack(C) if A > 1 else None
+    # every launch the ledger counts for the row: both maths, NORMALIZE and RAW
+    for run in inst.pricing_runs_of("basket path", case):
+        hw, norm = MATHS[run.math], (NORM if run.normalize else RAW)
+        assert _lib.lib().smc_basket_price_paths_kernel(A, T, P, hw, norm).decode() == run.name
+        ref = pc.reference(_oracle, A, T, P, B, run.math, run.normalize, spread)
+        # the condition on the inputs, before the kernel's output is looked at
+        assert pr.count_ok(ref.doubt[:, 0], P) and pr.count_ok(ref.doubt[:, 1], P), ref.doubt
+        got = _paths(rows, A, T, P, hw, norm, w=w, tri=tri, bars=bars)
+        _check(got, ref, f"paths A {A} T {T} P {P} {run.math} {'NORMALIZE' if norm else 'RAW'}")
 
 
 # ---- 1. against the float64 reference ----------------------------------------------------------------------------------
@@ -117,7 +120,11 @@ def test_path_kernel_spread_against_the_reference() -> None:
 
 
 # ---- 2. bit for bit against the price call -------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", pc.CASES + [(1, 3, 693, 6), (6, 4, 2049, 6), (7, 3, 100, 6)],
+EUROPEAN_EXTRA = [(1, 3, 693, 6), (6, 4, 2049, 6), (7, 3, 100, 6)]
+
+
+# a shape of EUROPEAN_EXTRA runs once, with its own B: the ids stay one per shape
+@pytest.mark.parametrize("case", [c for c in pc.CASES if c[:3] not in [e[:3] for e in EUROPEAN_EXTRA]] + EUROPEAN_EXTRA,
                          ids=lambda c: f"A{c[0]}-T{c[1]}-P{c[2]}")
 def test_european_columns_and_sums_are_the_price_call(case) -> None:
     A, T, P, B = case
@@ -314,7 +321,7 @@ def test_orderings(case) -> None:
     rows, w, C, bars = pc.inputs(_oracle, A, B, case == pc.SPREAD)
     for hw in MATHS.values():
         for norm in (NORM, RAW):
-            c = _paths(rows, A, T, P, hw, norm, w=w, tri=cases.pack(C), bars=bars)[0]
+            c = _paths(rows, A, T, P, hw, norm, w=w, tri=cases.pack(C) if A > 1 else None, bars=bars)[0]
             assert np.all(c[:, 2] <= c[:, 8]) and np.all(c[:, 3] <= c[:, 9])
             assert np.all(c[:, 4] >= c[:, 8]) and np.all(c[:, 5] >= c[:, 9])
             assert np.all(c[:, 24] <= c[:, 20]) and np.all(c[:, 20] <= c[:, 23])

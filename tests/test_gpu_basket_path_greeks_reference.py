@@ -23,6 +23,7 @@ from tests.helpers import basket_greeks_cases as eq_cases
 from tests.helpers import basket_path_greeks_cases as gc
 from tests.helpers import basket_path_greeks_reference as pg
 from tests.helpers import basket_reference as br
+from tests.helpers import instantiations as inst
 from tests.helpers import poisoned
 
 pytestmark = pytest.mark.gpu
@@ -66,21 +67,23 @@ def _against_reference(case, spread: bool) -> None:
     _oracle.build()
     rows, w, C = gc.inputs(A, B, spread)
     tri = cases.pack(C) if A > 1 else None
-    for math, hw in MATHS.items():
-        for norm in (NORM, RAW):
-            ref = gc.reference(_oracle, A, T, P, B, math, bool(norm), spread)
-            # the conditions on the inputs, before the kernel's output is looked at
-            assert pg.count_ok(ref.doubt_ind, P), ref.doubt_ind
-            assert pg.arg_ok(ref.doubt_arg, P), ref.doubt_arg
-            assert np.all(np.isfinite(ref.bound))
-            got = _greeks(rows, A, T, P, hw, norm, w, tri)
-            G = pg.kinds(A)
-            used = {"greeks": pg.share_used(got, ref, list(range(4 * G))),
-                    "greek errors": pg.share_used(got, ref, list(range(4 * G, 8 * G))),
-                    "prices": pg.share_used(got, ref, pg.price_columns(A))}
-            print(f"basket path greeks A {A} T {T} P {P} {math} {'NORMALIZE' if norm else 'RAW'}: share of the bound "
-                  "used " + ", ".join(f"{k} {v:.3f}" for k, v in used.items()))
-            assert max(used.values()) < 1.0, (case, math, norm, used)
+    # every launch the ledger counts for the row: both maths, NORMALIZE and RAW
+    for run in inst.pricing_runs_of("basket path greeks", case):
+        math, hw, norm = run.math, MATHS[run.math], (NORM if run.normalize else RAW)
+        assert _lib.lib().smc_basket_greeks_paths_kernel(A, T, P, hw, norm).decode() == run.name
+        ref = gc.reference(_oracle, A, T, P, B, math, bool(norm), spread)
+        # the conditions on the inputs, before the kernel's output is looked at
+        assert pg.count_ok(ref.doubt_ind, P), ref.doubt_ind
+        assert pg.arg_ok(ref.doubt_arg, P), ref.doubt_arg
+        assert np.all(np.isfinite(ref.bound))
+        got = _greeks(rows, A, T, P, hw, norm, w, tri)
+        G = pg.kinds(A)
+        used = {"greeks": pg.share_used(got, ref, list(range(4 * G))),
+                "greek errors": pg.share_used(got, ref, list(range(4 * G, 8 * G))),
+                "prices": pg.share_used(got, ref, pg.price_columns(A))}
+        print(f"basket path greeks A {A} T {T} P {P} {math} {'NORMALIZE' if norm else 'RAW'}: share of the bound "
+              "used " + ", ".join(f"{k} {v:.3f}" for k, v in used.items()))
+        assert max(used.values()) < 1.0, (case, math, norm, used)
 
 
 @pytest.mark.parametrize("case", gc.CASES, ids=lambda c: f"A{c[0]}-T{c[1]}-P{c[2]}")

@@ -23,6 +23,7 @@ import oracle as _oracle
 from spectralmc_amd import _lib
 from spectralmc_amd.basket import BasketConfig, BasketEngine, basket_price, basket_targets
 from tests.helpers import basket_reference as br
+from tests.helpers import instantiations as inst
 from tests.helpers import poisoned
 
 pytestmark = pytest.mark.gpu
@@ -197,25 +198,38 @@ def _check_price(got: tuple[np.ndarray, np.ndarray], ref: br.BasketRef, label: s
 
 
 def _price_against_reference(rows: np.ndarray, A: int, T: int, P: int, label: str) -> None:
+    """Every launch the ledger counts for the row (both maths, raw, lds and forced replay), each under the name the
+    library's own query gives it."""
     name = _lib.lib().smc_basket_price_kernel
-    for math, hw in (("portable", 0), ("hw", _lib.MATH_HW)):
-        for norm in (_lib.NORM_RAW, _lib.NORM_NORMALIZE):
-            ref = _reference(rows, A, T, P, math, normalize=norm == _lib.NORM_NORMALIZE)
-            modes = {name(A, T, P, hw, norm).decode(): hw}
-            if norm == _lib.NORM_NORMALIZE:
-                modes[name(A, T, P, hw | _lib.PRICE_REPLAY, norm).decode()] = hw | _lib.PRICE_REPLAY
-                assert set(modes) == {"basket_price_kernel(lds)", "basket_price_kernel(replay)"}
-            else:
-                assert set(modes) == {"basket_price_kernel(raw)"}
-            for mode, flags in modes.items():
-                _check_price(_price(rows, A, T, P, flags, norm), ref, f"{label} {math} {mode}")
+    refs = {}
+    for run in inst.pricing_runs_of("basket price", (A, T, P, rows.shape[0])):
+        flags = (_lib.MATH_HW if run.math == "hw" else 0) | (_lib.PRICE_REPLAY if run.force_replay else 0)
+        norm = _lib.NORM_NORMALIZE if run.normalize else _lib.NORM_RAW
+        assert name(A, T, P, flags, norm).decode() == run.name
+        if (run.math, run.normalize) not in refs:
+            refs[run.math, run.normalize] = _reference(rows, A, T, P, run.math, normalize=run.normalize)
+        _check_price(_price(rows, A, T, P, flags, norm), refs[run.math, run.normalize], f"{label} {run.math} {run.name}")
+
+
+# (A, T, P, B): a single path, a ragged chunk, one path into the second chunk and two full chunks at A = 1, 3, 4, 8;
+# then the asset counts those leave out, at the ledger's shape (one stream per group, a ragged lane, a partial chunk).
+# tests/test_instantiation_ledger.py holds this table to the ledger of instantiations
+PRICE_CASES = [(A, T, P, 6) for A, T in [(1, 3), (3, 5), (4, 16), (8, 2)] for P in [1, 693, 2049, 4096]]
+LEDGER_PRICE_CASES = [(2, 3, 693, 3), (5, 3, 693, 3), (6, 3, 693, 3), (7, 3, 693, 3)]
+PRICE_CASES += LEDGER_PRICE_CASES
 
 
 @pytest.mark.parametrize("P", [1, 693, 2049, 4096])
 @pytest.mark.parametrize("A,T", [(1, 3), (3, 5), (4, 16), (8, 2)])
 def test_price_kernel_columns_and_sums(A, T, P) -> None:
     """A single path, a ragged chunk, one path into the second chunk, two full chunks."""
+    assert (A, T, P, 6) in PRICE_CASES
     _price_against_reference(_sobol_rows(A, 6), A, T, P, f"price A {A} T {T} P {P}")
+
+
+@pytest.mark.parametrize("A,T,P,B", LEDGER_PRICE_CASES)
+def test_price_kernel_columns_and_sums_at_every_asset_count(A, T, P, B) -> None:
+    _price_against_reference(_sobol_rows(A, B), A, T, P, f"price A {A} T {T} P {P}")
 
 
 # ---- the hand-built rows -----------------------------------------------------------------------------------------------

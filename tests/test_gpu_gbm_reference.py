@@ -25,6 +25,7 @@ import oracle as _oracle
 from spectralmc_amd import _lib
 from spectralmc_amd.sobol_sampler import SobolEngine
 from tests.helpers import gbm_reference as gref
+from tests.helpers import instantiations as inst
 from tests.helpers import make_domain_bounds, poisoned
 from tests.test_gbm_reference import REST, SEED, case_rows
 
@@ -276,9 +277,12 @@ def test_price_kernel_columns(T, P, scheme) -> None:
     """smc_gbm_price raw, parked in LDS and replayed (forced with SMC_PRICE_REPLAY at these small P): the 8 columns,
     standard errors included."""
     name = _lib.lib().smc_gbm_price_kernel
+    runs = inst.pricing_runs_of("price f32", (T, P, scheme))  # every launch the ledger counts for the row
+    assert [r.name for r in runs] == 2 * ["price_kernel(raw)", "price_kernel(lds)", "price_kernel(replay)"]
     for math, (_, hw) in MATHS.items():
-        for normalize, mode, flag in ((False, "raw", 0), (True, "lds", 0), (True, "replay", _lib.PRICE_REPLAY)):
-            assert name(T, P, scheme | hw | flag, int(normalize), _lib.DTYPE_F32).decode() == f"price_kernel({mode})"
+        for run in (r for r in runs if r.math == math):
+            normalize, mode, flag = run.normalize, run.name[13:-1], (_lib.PRICE_REPLAY if run.force_replay else 0)
+            assert name(T, P, scheme | hw | flag, int(normalize), _lib.DTYPE_F32).decode() == run.name
             rows, _ = case_rows(scheme, normalize)
             ref = _ref(12, T, P, scheme, normalize, math)
             got = _price(rows, T, P, scheme | hw | flag, int(normalize))
@@ -301,9 +305,12 @@ def test_path_price_kernel_columns(T, P, scheme) -> None:
     about one standard deviation out (tests/test_gpu_path_price._barriers' rule), one contract has its upper barrier
     at the forward, inside the bulk, and the flat contract's sits on its paths where the bound is zero."""
     name = _lib.lib().smc_gbm_price_paths_kernel
+    runs = inst.pricing_runs_of("path price f32", (T, P, scheme))  # every launch the ledger counts for the row
+    assert [r.name for r in runs] == 2 * ["path_price_kernel(raw)", "path_price_kernel(replay)"]
     for math, (_, hw) in MATHS.items():
-        for normalize, mode in ((False, "raw"), (True, "replay")):
-            assert name(T, P, scheme | hw, int(normalize), _lib.DTYPE_F32).decode() == f"path_price_kernel({mode})"
+        for run in (r for r in runs if r.math == math):
+            normalize, mode = run.normalize, run.name[18:-1]
+            assert name(T, P, scheme | hw, int(normalize), _lib.DTYPE_F32).decode() == run.name
             rows, bars = case_rows(scheme, normalize)
             ref = _ref(12, T, P, scheme, normalize, math, bars=True)
             got = _price_paths(rows, bars, T, P, scheme | hw, int(normalize))

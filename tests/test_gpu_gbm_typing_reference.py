@@ -22,6 +22,7 @@ import torch
 import oracle as _oracle
 from spectralmc_amd import _lib
 from tests.helpers import gbm_reference as gref
+from tests.helpers import instantiations as inst
 from tests.helpers import poisoned
 from tests.test_gbm_reference import REST, SEED, case_rows
 
@@ -247,15 +248,36 @@ def _check_price(got: np.ndarray, ref: gref.GbmRef, label: str) -> None:
     assert max(used.values()) < 1.0, (label, used)
 
 
-@needs_longdouble
-@pytest.mark.parametrize("T,P", [(16, 4096), (5, 693)])
-def test_f64_price_kernel_columns(T, P) -> None:
+# (T, P, scheme): tests/test_instantiation_ledger.py holds the two tables to the ledger of instantiations; the simple
+# scheme's f64 instantiations have their row at the ragged shape
+F64_PRICE_CASES = [(16, 4096, LOG), (5, 693, LOG), (5, 693, SIMPLE)]
+F64_PATH_PRICE_CASES = [(16, 1024, LOG), (5, 693, LOG), (5, 693, SIMPLE)]
+
+
+def _f64_price_kernel_columns(T: int, P: int, scheme: int) -> None:
+    """Every launch the ledger counts for the row: raw, lds and forced replay."""
     name = _lib.lib().smc_gbm_price_kernel
-    for normalize, mode, flag in ((False, "raw", 0), (True, "lds", 0), (True, "replay", _lib.PRICE_REPLAY)):
-        assert name(T, P, LOG | flag, int(normalize), F64).decode() == f"price_kernel({mode})"
-        rows, _ = _rows(12, LOG, normalize)
-        ref = _ref("f64", 12, T, P, LOG, normalize)
-        _check_price(_price(rows, T, P, LOG | flag, int(normalize)), ref, f"price_kernel({mode}) f64 T {T} P {P}")
+    runs = inst.pricing_runs_of("price f64", (T, P, scheme))
+    assert [r.name for r in runs] == ["price_kernel(raw)", "price_kernel(lds)", "price_kernel(replay)"]
+    for run in runs:
+        flag, normalize = (_lib.PRICE_REPLAY if run.force_replay else 0), run.normalize
+        assert name(T, P, scheme | flag, int(normalize), F64).decode() == run.name
+        rows, _ = _rows(12, scheme, normalize)
+        ref = _ref("f64", 12, T, P, scheme, normalize)
+        _check_price(_price(rows, T, P, scheme | flag, int(normalize)), ref,
+                     f"{run.name} f64 T {T} P {P} {'log' if scheme == LOG else 'simple'}")
+
+
+@needs_longdouble
+@pytest.mark.parametrize("T,P", [c[:2] for c in F64_PRICE_CASES if c[2] == LOG])
+def test_f64_price_kernel_columns(T, P) -> None:
+    _f64_price_kernel_columns(T, P, LOG)
+
+
+@needs_longdouble
+@pytest.mark.parametrize("T,P", [c[:2] for c in F64_PRICE_CASES if c[2] == SIMPLE])
+def test_f64_price_kernel_columns_simple_euler(T, P) -> None:
+    _f64_price_kernel_columns(T, P, SIMPLE)
 
 
 @needs_longdouble
@@ -269,22 +291,24 @@ def test_f64_price_kernel_replays_beyond_the_park_bound() -> None:
     _check_price(_price(rows, T, P, LOG, 1), ref, f"price_kernel(replay) f64 T {T} P {P} B {B}")
 
 
-@needs_longdouble
-@pytest.mark.parametrize("T,P", [(16, 1024), (5, 693)])
-def test_f64_path_price_kernel_columns(T, P) -> None:
+def _f64_path_price_kernel_columns(T: int, P: int, scheme: int) -> None:
+    """Every launch the ledger counts for the row: raw and the NORMALIZE replay."""
     name = _lib.lib().smc_gbm_price_paths_kernel
-    for normalize, mode in ((False, "raw"), (True, "replay")):
-        assert name(T, P, LOG, int(normalize), F64).decode() == f"path_price_kernel({mode})"
-        rows, bars = _rows(12, LOG, normalize)
-        ref = _ref("f64", 12, T, P, LOG, normalize, bars=True)
+    runs = inst.pricing_runs_of("path price f64", (T, P, scheme))
+    assert [r.name for r in runs] == ["path_price_kernel(raw)", "path_price_kernel(replay)"]
+    for run in runs:
+        normalize = run.normalize
+        assert name(T, P, scheme, int(normalize), F64).decode() == run.name
+        rows, bars = _rows(12, scheme, normalize)
+        ref = _ref("f64", 12, T, P, scheme, normalize, bars=True)
         cd = torch.tensor(rows, dtype=torch.float64, device=DEV)
         bd = torch.tensor(bars, dtype=torch.float64, device=DEV)
         out = poisoned((12, _lib.PATH_PRICE_COLS), torch.float64, DEV)
-        _lib.check(_lib.lib().smc_gbm_price_paths(_lib.ptr(cd), _lib.ptr(bd), 12, T, P, SEED, None, ORD0, LOG,
+        _lib.check(_lib.lib().smc_gbm_price_paths(_lib.ptr(cd), _lib.ptr(bd), 12, T, P, SEED, None, ORD0, scheme,
                                                   int(normalize), F64, _lib.ptr(out), None))
         torch.cuda.synchronize()
         got = out.cpu().numpy()
-        label = f"path_price_kernel({mode}) f64 T {T} P {P}"
+        label = f"{run.name} f64 T {T} P {P} {'log' if scheme == LOG else 'simple'}"
         assert not np.isnan(got).any(), label
         means = [c for c in REST if c < 8 or c >= 16]
         used = {"means": gref.share_used(got[:, means], ref.path[:, means], ref.path_bound[:, means]),
@@ -294,3 +318,15 @@ def test_f64_path_price_kernel_columns(T, P) -> None:
               + f"; paths in doubt {ref.doubt.tolist()}")
         assert used["knocked share"] <= 1.0, (label, used)  # a count: it may use its whole tolerance
         assert max(used["means"], used["stderr"]) < 1.0, (label, used)
+
+
+@needs_longdouble
+@pytest.mark.parametrize("T,P", [c[:2] for c in F64_PATH_PRICE_CASES if c[2] == LOG])
+def test_f64_path_price_kernel_columns(T, P) -> None:
+    _f64_path_price_kernel_columns(T, P, LOG)
+
+
+@needs_longdouble
+@pytest.mark.parametrize("T,P", [c[:2] for c in F64_PATH_PRICE_CASES if c[2] == SIMPLE])
+def test_f64_path_price_kernel_columns_simple_euler(T, P) -> None:
+    _f64_path_price_kernel_columns(T, P, SIMPLE)

@@ -21,6 +21,7 @@ from spectralmc_amd import _lib
 from tests.helpers import ATOL_FLOAT64, RTOL_FLOAT64, poisoned
 from tests.helpers import gbm_reference as gref
 from tests.helpers import greeks_reference as gk
+from tests.helpers import instantiations as inst
 from tests.test_greeks_reference import ORD0, SEED, case_rows, degenerate_rows
 
 pytestmark = pytest.mark.gpu
@@ -94,6 +95,10 @@ CASES = [
 def test_greeks_kernel_within_the_bound(mode, B, T, P, flags) -> None:
     if P == F32_PARK + 1:
         assert _name(T, F32_PARK, 0, NORM, _lib.DTYPE_F32) == "greeks_kernel(lds)"
+    # the launches the ledger counts for the row are the ones _hold makes: both maths in the mode the row states
+    runs = inst.pricing_runs_of("greeks f32", (mode, B, T, P, flags))
+    assert [(r.math, r.name, r.force_replay, r.normalize) for r in runs] == \
+        [(m, f"greeks_kernel({mode})", bool(flags), mode != "raw") for m in MATHS]
     _hold(_rows(B), T, P, mode, flags, RAW if mode == "raw" else NORM)
 
 
@@ -109,13 +114,19 @@ def test_greeks_kernel_degenerate_rows_within_the_bound(mode, flags, norm) -> No
 
 
 # the last shape lies just under the f64 park bound
-@pytest.mark.parametrize("T,P", [(16, 4096), (5, 693), (2, F64_PARK - 36)])
+F64_CASES = [(16, 4096), (5, 693), (2, F64_PARK - 36)]
+
+
+@pytest.mark.parametrize("T,P", F64_CASES)
 def test_greeks_kernel_f64_against_the_reference(T, P) -> None:
     _oracle.build()
     rows = _rows(12)
     assert _name(T, F64_PARK, 0, NORM, _lib.DTYPE_F64) == "greeks_kernel(lds)"
     assert _name(T, F64_PARK + 1, 0, NORM, _lib.DTYPE_F64) == "greeks_kernel(replay)"
-    for mode, flags, norm in (("raw", 0, RAW), ("lds", 0, NORM), ("replay", _lib.PRICE_REPLAY, NORM)):
+    runs = inst.pricing_runs_of("greeks f64", (T, P))  # every launch the ledger counts for the row
+    assert [r.name for r in runs] == ["greeks_kernel(raw)", "greeks_kernel(lds)", "greeks_kernel(replay)"]
+    for run in runs:
+        mode, flags, norm = run.name[14:-1], (_lib.PRICE_REPLAY if run.force_replay else 0), (NORM if run.normalize else RAW)
         ref = _f64_reference(T, P, norm == NORM)
         assert _name(T, P, flags, norm, _lib.DTYPE_F64) == f"greeks_kernel({mode})"
         got = _greeks(rows, T, P, flags, norm, _lib.DTYPE_F64)

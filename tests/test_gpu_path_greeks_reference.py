@@ -17,6 +17,7 @@ import oracle as _oracle
 from spectralmc_amd import _lib
 from tests.helpers import gbm_reference as gref
 from tests.helpers import greeks_reference as gk
+from tests.helpers import instantiations as inst
 from tests.helpers import path_greeks_reference as pg
 from tests.helpers import poisoned
 from tests.helpers.path_greeks_cases import CASES, FLAT_ROWS, ORD0, ROWS, SEED
@@ -51,11 +52,19 @@ def _ref(T: int, P: int, norm: int, math: str) -> pg.PathGreeksRef:
 SHAPES = {"portable": CASES + [(37, 693)], "hw": CASES + [(37, 693)], "f64": CASES + [(29, 693)]}
 
 
+# (math, T, P): tests/test_instantiation_ledger.py holds the table to the ledger of instantiations
+SHAPE_CASES = [(m, T, P) for m in MODES for T, P in SHAPES[m]]
+
+
 @pytest.mark.parametrize("norm", [0, 1])
-@pytest.mark.parametrize("math,T,P", [(m, T, P) for m in MODES for T, P in SHAPES[m]])
+@pytest.mark.parametrize("math,T,P", SHAPE_CASES)
 def test_path_greeks_within_the_reference_bound(math, T, P, norm) -> None:
     if math == "f64" and not gref.LONGDOUBLE_OK:
         pytest.skip("the f64 kernel's reference needs a long double with a 64-bit significand")
+    # the launch is one the ledger counts for the row, under the name the library's query gives it
+    run, = (r for r in inst.pricing_runs_of("path greeks", (math, T, P)) if r.normalize == bool(norm))
+    assert (run.dtype, run.math) == (("f64", "portable") if math == "f64" else ("f32", math))
+    assert _lib.lib().smc_gbm_greeks_paths_kernel(T, P, MODES[math][0], norm, MODES[math][1]).decode() == run.name
     ref = _ref(T, P, norm, math)
     assert gref.count_ok(ref.doubt_ind, P) and pg.arg_ok(ref.doubt_arg, P)
     got = _greeks(ROWS, T, P, math, norm)

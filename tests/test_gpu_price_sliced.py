@@ -24,6 +24,7 @@ from spectralmc_amd.effects import PathScheme
 from spectralmc_amd.gbm import BlackScholes
 from spectralmc_amd.models.numerical import Precision
 from tests.helpers import gbm_reference as gref
+from tests.helpers import instantiations as inst
 from tests.helpers import (
     assert_rows_equal,
     expect_success,
@@ -187,22 +188,44 @@ def _check_reference(got: np.ndarray, ref: gref.GbmRef, label: str) -> None:
 @pytest.mark.parametrize("T,P,span,scheme", SLICED_CASES)
 def test_sliced_within_the_reference_bound_f32(T, P, span, scheme, math) -> None:
     flag, dtype = MATHS[math]
-    for normalize in (False, True):
+    # the calls the ledger counts for the row in this math: RAW (Raw, finish) and NORMALIZE (Sum, finish, Pay, finish)
+    runs = [r for r in inst.pricing_runs_of("sliced f32", (T, P, span, scheme)) if r.math == math]
+    assert [r.normalize for r in runs] == [False, True]
+    for run in runs:
+        normalize = run.normalize
+        assert _lib.lib().smc_gbm_price_sliced_kernel(T, P, span, scheme | flag, int(normalize), dtype).decode() == run.name
         ref = reference(T, P, scheme, normalize, math)  # before the kernel's output is looked at
         got = _sliced(_rows(scheme, normalize), T, P, span, scheme | flag, int(normalize), dtype)
         _check_reference(got, ref, f"price_slice_kernel {math} T {T} P {P} slice {span} "
                                    f"{'log' if scheme == LOG else 'simple'} {'NORM' if normalize else 'RAW'}")
 
 
+# (T, P, slice_paths, scheme): W = 3, last slice of 693 paths; the simple scheme's f64 instantiations at two slices
+F64_SLICED_CASES = [(16, 4789, 2048, LOG), (5, 2741, 2048, SIMPLE)]
+
+
+def _sliced_within_the_reference_bound_f64(T: int, P: int, span: int, scheme: int) -> None:
+    _oracle.build()
+    runs = inst.pricing_runs_of("sliced f64", (T, P, span, scheme))  # the calls the ledger counts for the row
+    assert [r.normalize for r in runs] == [False, True]
+    for run in runs:
+        normalize = run.normalize
+        assert _lib.lib().smc_gbm_price_sliced_kernel(T, P, span, scheme, int(normalize), F64).decode() == run.name
+        rows = _rows(scheme, normalize)
+        ref = gref.reference(_oracle, rows, T, P, SEED, ORD0, scheme=scheme, eps=gref.F64_ENGINE, normalize=normalize)
+        got = _sliced(rows, T, P, span, scheme, int(normalize), F64)
+        _check_reference(got, ref, f"price_slice_kernel f64 T {T} P {P} slice {span} "
+                                   f"{'log' if scheme == LOG else 'simple'} {'NORM' if normalize else 'RAW'}")
+
+
 @needs_longdouble
 def test_sliced_within_the_reference_bound_f64() -> None:
-    T, P, span = 16, 4789, 2048  # W = 3, last slice of 693 paths
-    _oracle.build()
-    for normalize in (False, True):
-        rows = _rows(LOG, normalize)
-        ref = gref.reference(_oracle, rows, T, P, SEED, ORD0, scheme=LOG, eps=gref.F64_ENGINE, normalize=normalize)
-        got = _sliced(rows, T, P, span, LOG, int(normalize), F64)
-        _check_reference(got, ref, f"price_slice_kernel f64 T {T} P {P} slice {span} {'NORM' if normalize else 'RAW'}")
+    _sliced_within_the_reference_bound_f64(*F64_SLICED_CASES[0])
+
+
+@needs_longdouble
+def test_sliced_within_the_reference_bound_f64_simple_euler() -> None:
+    _sliced_within_the_reference_bound_f64(*F64_SLICED_CASES[1])
 
 
 # ---- 5. degenerate contracts and P = 1 ---------------------------------------------------------------------------------
