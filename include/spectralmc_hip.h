@@ -1013,9 +1013,9 @@ int32_t smc_basket_greeks_paths_cols(int32_t n_assets);
  * SMC_ERR_INVALID_ARGUMENT (there is no mode to force); slice_paths <= 0 or not a multiple of 2048:
  * SMC_ERR_INVALID_SHAPE; W > 65,535 or n_contracts W >= 2^31: SMC_ERR_INVALID_SHAPE; NULL workspace_dev or
  * workspace_bytes below the query: SMC_ERR_INVALID_ARGUMENT.
- * Out of scope: sliced Greeks and sliced path-dependent or basket pricing (the same pattern with more partials; the
- * workspace layout [B][W][k] and the slice rule are meant to carry over); parking slices to save the NORMALIZE
- * replay; a slice length chosen from the batch size. */
+ * Out of scope: sliced path-dependent or basket pricing (the same pattern with more partials; the workspace layout
+ * [B][W][k] and the slice rule are meant to carry over, as they did to smc_gbm_greeks_sliced below); parking slices
+ * to save the NORMALIZE replay; a slice length chosen from the batch size. */
 int32_t smc_gbm_price_sliced(const double* contracts_dev /*[B][6]*/, int64_t n_contracts, int32_t timesteps,
                              int64_t n_paths, int64_t slice_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
                              int64_t ordinal0, int32_t scheme, int32_t normalization, int32_t dtype,
@@ -1032,6 +1032,53 @@ int64_t     smc_gbm_price_slice_paths(int64_t n_paths);
  * the call rejects).  Static string, no device call. */
 const char* smc_gbm_price_sliced_kernel(int32_t timesteps, int64_t n_paths, int64_t slice_paths, int32_t scheme,
                                         int32_t normalization, int32_t dtype);
+
+/* ---- sliced batched Greeks: one contract's Greeks across workgroups (additive under ABI 21) -----
+ * smc_gbm_greeks' 26 columns (SMC_GREEKS_COLS: the same per-path table, constants and conventions for v = 0, T = 0
+ * and n_paths = 1) in smc_gbm_price_sliced's geometry: W = ceil(n_paths / slice_paths) slices of slice_paths paths (a
+ * positive multiple of 2048; the last slice is ragged and ends at n_paths), workgroup b W + w for slice w of contract
+ * b, the streams (seed, ordinal, p0 / 4, timesteps) with the contract-global p0; lanes wholly past the slice end
+ * neither draw nor contribute.  Log-Euler only, SMC_MATH_HW f32 only.  The default slice length is
+ * smc_gbm_price_slice_paths(n_paths): there is no second rule, so a price and its Greeks are cut identically.
+ * Order.  Inside a slice, smc_gbm_greeks' order over the slice's own chunks (per lane over the chunks ascending, the
+ * wave butterfly xor 32..1, waves 0..7).  A workgroup leaves up to 22 f64 partials in the workspace: the 20 sums of
+ * the ten per-path terms and their squares, the raw terminal sum (the lane's 4 values summed in the sim dtype first)
+ * and, under SMC_NORM_NORMALIZE, sum f64(x L).  Each total of a contract is slice 0's value, then + slice 1, ...,
+ * + slice W - 1 (greeks_finish_kernel, one thread per total); the columns are smc_gbm_greeks' closing arithmetic on
+ * the totals: mean and standard error per term, gamma and its error from vega over v T X0^2 in f64, columns 24 / 25
+ * the total raw sum / sum x L (column 25 is 0 under SMC_NORM_RAW).  Under SMC_NORM_NORMALIZE the payoff scale and the
+ * constants of the weights come from the contract's two totals, exactly as smc_gbm_greeks takes them from its sums.
+ * Promises.  The block is bit-identical run to run, under any split of the batch, and whatever the workspace held.
+ * For slice_paths >= n_paths (W = 1) it is smc_gbm_greeks | SMC_PRICE_REPLAY's bit for bit (under SMC_NORM_RAW:
+ * greeks_kernel(raw)'s).  At any W, columns 20, 21, 22, 23, 24 are smc_gbm_price_sliced's columns 0, 1, 3, 4, 7 at the
+ * same slice_paths, bit for bit (the same per-path values in the same order).  At W > 1 the other columns may differ
+ * from smc_gbm_greeks' in their last bits only: the f64 sums are associated by slice.
+ * Launches, in stream order on `stream`: SMC_NORM_RAW two (greeks_slice_kernel: the raw sum and the 20 sums at scale
+ * 1; greeks_finish_kernel); SMC_NORM_NORMALIZE four (greeks_slice_kernel for the two sums; greeks_finish_kernel for
+ * the totals; greeks_slice_kernel again, replaying its slice's streams; greeks_finish_kernel for the columns).  No
+ * atomics, no arrival counters, no waiting on memory, no assumption that workgroups are co-resident; capturable into
+ * a graph; no allocation, no synchronisation; no parked mode.
+ * workspace_dev: smc_gbm_greeks_sliced_workspace_bytes bytes = 8 n_contracts (22 W + 2), 8-byte aligned: partials
+ * [B][W][22], then totals [B][2].  It needs no zeroing (every slot read was written earlier in the same call) and
+ * holds nothing between calls.
+ * Checks, in this order, all before the empty batch (n_contracts = 0: SMC_OK, nothing touched) is accepted:
+ * smc_gbm_greeks' (NULL contracts_dev: SMC_ERR_INVALID_ARGUMENT; n_contracts < 0 or >= 2^31, timesteps <= 0,
+ * n_paths <= 0 or >= 2^40: SMC_ERR_INVALID_SHAPE; dtype, NULL greeks_dev, bad scheme or unknown flag, SMC_MATH_REF,
+ * SMC_MATH_HW with f64, bad normalization, SMC_SCHEME_SIMPLE_EULER: SMC_ERR_INVALID_ARGUMENT); SMC_PRICE_REPLAY or
+ * SMC_TRAIN_DYNAMIC: SMC_ERR_INVALID_ARGUMENT (there is no mode to force); then smc_gbm_price_sliced's slice_paths,
+ * W <= 65,535, n_contracts W < 2^31 and workspace checks, with its codes.
+ * Out of scope: sliced Greeks of the path-dependent or basket payoffs; parking slices; simple Euler. */
+int32_t smc_gbm_greeks_sliced(const double* contracts_dev /*[B][6]*/, int64_t n_contracts, int32_t timesteps,
+                              int64_t n_paths, int64_t slice_paths, uint64_t mc_seed, const int64_t* ordinal_dev,
+                              int64_t ordinal0, int32_t scheme, int32_t normalization, int32_t dtype,
+                              double* greeks_dev /*[B][26]*/, void* workspace_dev, int64_t workspace_bytes,
+                              void* stream);
+/* 8 n_contracts (22 W + 2); -1 for the arguments smc_gbm_price_sliced_workspace_bytes rejects. */
+int64_t     smc_gbm_greeks_sliced_workspace_bytes(int64_t n_contracts, int64_t n_paths, int64_t slice_paths);
+/* "greeks_slice_kernel(raw)", "greeks_slice_kernel(replay)" or "unsupported" (a shape, scheme, normalization or dtype
+ * the call rejects).  Static string, no device call. */
+const char* smc_gbm_greeks_sliced_kernel(int32_t timesteps, int64_t n_paths, int64_t slice_paths, int32_t scheme,
+                                         int32_t normalization, int32_t dtype);
 
 #ifdef __cplusplus
 }

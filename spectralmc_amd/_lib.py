@@ -135,6 +135,10 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "smc_gbm_price_sliced_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
     "smc_gbm_price_slice_paths": (_c_i64, [_c_i64]),
     "smc_gbm_price_sliced_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32]),
+    "smc_gbm_greeks_sliced": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i64, _c_i64, _c_u64, _c_vp, _c_i64, _c_i32, _c_i32,
+                                       _c_i32, _c_vp, _c_vp, _c_i64, _c_vp]),
+    "smc_gbm_greeks_sliced_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "smc_gbm_greeks_sliced_kernel": (ctypes.c_char_p, [_c_i32, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32]),
 }
 
 # include/spectralmc_hip_testing.h: test-only entry points, inert unless SMC_ENABLE_TEST_HOOKS=1

@@ -2754,6 +2754,7 @@ __global__ __launch_bounds__(256) void normals_kernel(uint64_t seed, uint64_t or
   }
 }
 
+#ifndef SMC_GBM_DEVICE_ONLY  // gbm_greeks_sliced.hip includes the device code above and stops here
 // ---- host-side launch helpers ------------------------------------------------------------
 size_t lds_bytes(int T, int N, bool cf) {
   size_t doubles = static_cast<size_t>(T);                       // lds_tot
@@ -3974,3 +3975,7 @@ int32_t smc_test_path_greeks_plan(int32_t timesteps, int32_t scheme, int32_t nor
 
 #pragma GCC visibility pop
 }  // extern "C"
+#else  // SMC_GBM_DEVICE_ONLY
+}  // namespace
+}  // namespace smc
+#endif

@@ -762,6 +762,76 @@ class BlackScholes:
         names = list(self.BatchGreeks.model_fields)
         return Success([self.HostGreeks(**dict(zip(names, row))) for row in res.value.cpu().tolist()])
 
+    # ------------------------------------------------------------------ sliced batched Greeks
+    def _greeks_sliced_block(self, contracts: torch.Tensor, slice_paths: int | None
+                             ) -> Result[torch.Tensor, NormalsError]:
+        """One ``smc_gbm_greeks_sliced`` call on the current stream (no sync): the ``[B, 26]`` f64 block of
+        contracts ``[B, 6]`` f64 on the device, each contract cut into slices of ``slice_paths`` paths
+        (``None``: ``smc_gbm_price_slice_paths``, the price call's rule), one workgroup per slice; contract b
+        takes ordinal ``ordinal + b``.  The workspace comes from the caching allocator."""
+        if self._cfg.path_scheme is not PathScheme.LOG_EULER:
+            raise ValueError(f"greeks_sliced needs PathScheme.LOG_EULER, got {self._cfg.path_scheme.name}: the pathwise "
+                             "Greeks are functions of the log-Euler terminal value")
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if contracts.ndim != 2 or contracts.shape[1] != len(FIELDS) or contracts.dtype != torch.float64:
+            raise ValueError(f"contracts must be a [B, {len(FIELDS)}] float64 tensor, got "
+                             f"{tuple(contracts.shape)} {contracts.dtype}")
+        _lib.require_device()
+        if not contracts.is_cuda:
+            raise ValueError("contracts must be a device tensor")
+        sp = self._sp
+        contracts = contracts.contiguous()
+        B = int(contracts.shape[0])
+        block = torch.empty((B, _lib.GREEKS_COLS), dtype=torch.float64, device=contracts.device)
+        if self.price_batch_math not in ("portable", "hw"):
+            raise ValueError(f"price_batch_math must be 'portable' or 'hw', got {self.price_batch_math!r}")
+        scheme = scheme_code(self._cfg.path_scheme) | (_lib.MATH_HW if self.price_batch_math == "hw" else 0)
+        L = _lib.lib()
+        P = sp.total_paths()
+        span = int(L.smc_gbm_price_slice_paths(P)) if slice_paths is None else int(slice_paths)
+        if B:
+            nbytes = int(L.smc_gbm_greeks_sliced_workspace_bytes(B, P, span))
+            if nbytes < 0:
+                raise ValueError(f"slice_paths must be a positive multiple of 2048 that cuts {P} paths into at most "
+                                 f"65,535 slices (fewer than 2^31 workgroups in all), got {span}")
+            workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=contracts.device)
+            _lib.check(L.smc_gbm_greeks_sliced(
+                _lib.ptr(contracts), B, sp.timesteps, P, span, sp.mc_seed, None, self._served,
+                scheme, normalization_code(self._cfg.normalization), dtype_code(sp.dtype),
+                _lib.ptr(block), _lib.ptr(workspace), nbytes, _lib.stream_handle()))
+            self._served += B
+        return Success(block)
+
+    def greeks_sliced_device(self, contracts: torch.Tensor, slice_paths: int | None = None
+                             ) -> Result["BlackScholes.BatchGreeks", NormalsError]:
+        """``greeks_batch_device`` with every contract spread over ``ceil(P / slice_paths)`` workgroups, cut as
+        ``price_sliced_device`` cuts it: for one contract, or a few dozen, at a path count where one workgroup per
+        contract leaves the chip idle.  Device tensors in and out, the current stream, no host sync.  With one slice
+        the values are ``greeks_batch_device``'s bits; with more, the f64 sums are added slice by slice and the last
+        bits may differ (the price columns stay ``price_sliced_device``'s bit for bit)."""
+        res = self._greeks_sliced_block(contracts, slice_paths)
+        if isinstance(res, Failure):
+            return res
+        return Success(self.BatchGreeks(**dict(zip(self.BatchGreeks.model_fields, res.value.unbind(dim=1)))))
+
+    def greeks_sliced(self, inputs: "Sequence[BlackScholes.Inputs]", slice_paths: int | None = None
+                      ) -> Result["list[BlackScholes.HostGreeks]", NormalsError]:
+        """``greeks_batch`` through the sliced call: one device-to-host copy."""
+        if self._cfg.path_scheme is not PathScheme.LOG_EULER:
+            raise ValueError(f"greeks_sliced needs PathScheme.LOG_EULER, got {self._cfg.path_scheme.name}: the pathwise "
+                             "Greeks are functions of the log-Euler terminal value")
+        if self._normals_error is not None:
+            return Failure(NormalsUnavailable(error=self._normals_error))
+        if len(inputs) == 0:
+            return Success([])
+        rows = [[float(getattr(c, f)) for f in FIELDS] for c in inputs]
+        res = self._greeks_sliced_block(torch.tensor(rows, dtype=torch.float64, device=self._device()), slice_paths)
+        if isinstance(res, Failure):
+            return res
+        names = list(self.BatchGreeks.model_fields)
+        return Success([self.HostGreeks(**dict(zip(names, row))) for row in res.value.cpu().tolist()])
+
     # ------------------------------------------------------------------ batched Greeks of the path payoffs
     def _greeks_paths_block(self, contracts: torch.Tensor) -> Result[torch.Tensor, NormalsError]:
         """One ``smc_gbm_greeks_paths`` launch on the current stream (no sync): the ``[B, 40]`` f64 block of
